@@ -13,6 +13,12 @@ Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus 
 each rank trains on its own batch of 8 (weak scaling) with a real gradient
 all-reduce; the timed region is bracketed by barrier + synchronize and the max
 over ranks is reported.
+
+A plain run (``bench.py --gpus 1 --steps N --warmup W``) sets up, warms up, times the
+N train steps and prints the result line.  ``--full`` adds every other leg: the FM /
+DDPM samplers, the per-kernel rooflines, configs E and D and the CPU baseline (each
+still switchable with its ``--no-*`` flag).  ``--dump-outputs DIR`` writes what the
+last timed step produced (``dump_outputs``) so two builds can be compared.
 """
 from __future__ import annotations
 
@@ -280,6 +286,34 @@ def cpu_baseline(iters=3, batch=2, sampler_steps=3):
                        f"to the 50-step loop)")
 
 
+DUMP_SAMPLE = 1 << 21   # elements of each flat buffer written by --dump-outputs (8 MB as float32)
+
+
+def dump_outputs(out_dir, model, loss):
+    """What a caller of the timed step holds after its last call, as float32 ``<name>.npy`` under ``out_dir``:
+    ``loss`` (the step's return value), and fixed samples of the updated parameters (``params_sample``) and of
+    the step's gradients (``grads_sample``).  Both are taken at the same ``DUMP_SAMPLE`` seeded positions
+    (``sample_index``, int64 stored as float64) of the concatenation in ``model.parameters()`` order: the full
+    buffers are 452 MB each.  Inputs, initial weights and the in-step noise draws are seeded, so two runs with the
+    same arguments dump the result of the same computation."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = list(model.parameters())
+    total = sum(p.numel() for p in params)
+    idx = np.sort(np.random.default_rng(20240607).integers(0, total, size=min(DUMP_SAMPLE, total)))
+    sel = torch.from_numpy(idx).to(params[0].device)
+    with torch.no_grad():
+        flat_p = torch.cat([p.detach().reshape(-1) for p in params]).float()
+        flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params]).float()
+        arrays = {"loss": loss.detach().float().reshape(-1).cpu().numpy(),
+                  "params_sample": flat_p[sel].cpu().numpy(),
+                  "grads_sample": flat_g[sel].cpu().numpy(),
+                  "sample_index": idx.astype(np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 def _launch_ranks(n: int) -> int:
     """Run this script under ``python -m torch.distributed.run --nproc-per-node n`` (rendezvous on 127.0.0.1, a
     free port) as a child process; returns its exit code.  Called before any GPU work in this process."""
@@ -309,7 +343,15 @@ def main():
     ap.add_argument("--no-roofline", action="store_true", help="skip the per-kernel roofline legs")
     ap.add_argument("--no-config-e", action="store_true", help="skip the config E (3-D 128^3) leg")
     ap.add_argument("--no-config-d", action="store_true", help="skip the config D (latent diffusion) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the sampler, roofline, config E, config D and CPU-baseline legs (the --no-* flags "
+                         "switch single legs off again); without it only the timed train steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss and seeded samples of the updated "
+                         "parameters and of the gradients as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_sampler = args.no_roofline = args.no_config_e = args.no_config_d = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `bench.py --gpus N` outside a launcher: start N rank processes (torch.distributed.run, the reference's
@@ -381,6 +423,10 @@ def main():
     ms_step = dt / args.steps * 1e3
     train_ips = world * B * args.steps / dt
     log(f"[bench] train: {ms_step:.2f} ms/step, {train_ips:.2f} img/s (world {world}), loss {loss_v:.4f}")
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, model, loss)
+        log(f"[bench] wrote {sorted(dumped)} to {args.dump_outputs}")
 
     samp = {}
     if not args.no_sampler:
@@ -484,6 +530,8 @@ def main():
                                " EfficientUNetND 113M, concatenate conditioning) + 50-step FlowMatchEuler sampler",
                    "global_batch": world * B, "per_gpu_batch": B, "img": HW, "parallelism": f"dp{world}",
                    "hipgraph": use_graph},
+        "full": args.full,
+        "dumped_outputs": dumped,
         "train_loss": loss_v,
         "train_mfma_frac": step_tflops / PEAK_BF16_TFLOPS,
         **samp,

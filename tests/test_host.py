@@ -274,6 +274,36 @@ def test_bench_pmc_traffic_matches_timed_kernel_only():
     assert bench.pmc_traffic("conv3x3_halo9b<false, 2, 0, 8>") is None   # the 8-row instance: not the timed one
 
 
+def test_bench_dump_outputs_writes_seeded_float32_samples(tmp_path):
+    """bench.py --dump-outputs: the loss plus samples of parameters and gradients taken at the same seeded
+    positions of the ``model.parameters()`` concatenation, float32 .npy files, identical from call to call."""
+    import importlib.util
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.Linear(5, 3))
+    for p in model.parameters():
+        p.grad = torch.randn_like(p)
+    loss = torch.tensor([0.25])
+    shapes = bench.dump_outputs(str(tmp_path / "a"), model, loss)
+    bench.dump_outputs(str(tmp_path / "b"), model, loss)
+    assert sorted(shapes) == ["grads_sample", "loss", "params_sample", "sample_index"]
+    flat_p = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).numpy()
+    flat_g = torch.cat([p.grad.reshape(-1) for p in model.parameters()]).numpy()
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in shapes}
+    idx = got["sample_index"].astype(np.int64)
+    assert got["loss"].dtype == np.float32 and got["loss"].tolist() == [0.25]
+    assert got["params_sample"].dtype == np.float32 and got["grads_sample"].dtype == np.float32
+    assert idx.shape == (flat_p.size,) and idx.min() >= 0 and idx.max() < flat_p.size and (np.diff(idx) >= 0).all()
+    assert np.array_equal(got["params_sample"], flat_p[idx]) and np.array_equal(got["grads_sample"], flat_g[idx])
+    for n in shapes:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy"))
+    # the sample of the benched model stays far below the 64 MB an output dump may take
+    assert bench.DUMP_SAMPLE * (4 + 4 + 8) + 4 <= 64 << 20
+
+
 def test_tuning_table_and_override(monkeypatch):
     """runtime/tuning.py: every dispatch constant in one table, FMD_TUNE the only override; unknown names raise
     (a typo must not silently measure the default)."""

@@ -4,8 +4,9 @@
 # timing.  RCCL itself needs one GPU per rank and is exercised only by the driver's multi-GPU runs.
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+OUT=${OUT:-out}   # where this script leaves its results
+mkdir -p $OUT
 FMD_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node ${NPROC:-2} \
-  --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus ${NPROC:-2} --steps 10 --warmup 3 --sampler-steps 10 \
-  > gpurun_out/dp_rehearsal.json 2> gpurun_out/dp_rehearsal.err
-rc=$?; echo "dp rehearsal rc=$rc"; grep "\[bench\]" gpurun_out/dp_rehearsal.err; exit $rc
+  --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus ${NPROC:-2} --full --steps 10 --warmup 3 --sampler-steps 10 \
+  > $OUT/dp_rehearsal.json 2> $OUT/dp_rehearsal.err
+rc=$?; echo "dp rehearsal rc=$rc"; grep "\[bench\]" $OUT/dp_rehearsal.err; exit $rc

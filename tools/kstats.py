@@ -1,6 +1,6 @@
 """Per-step kernel breakdown from a rocprofv3 kernel trace (host-side analysis helper).
 
-usage: python tools/kstats.py gpurun_out/prof/run_kernel_trace.csv [--marker adamw_sched] [--top 40] [--shapes]
+usage: python tools/kstats.py out/prof/run_kernel_trace.csv [--marker adamw_sched] [--top 40] [--shapes]
 Takes the span between the last two launches of ``marker`` (one train step) and aggregates by kernel.
 """
 import argparse

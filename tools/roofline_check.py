@@ -1,6 +1,7 @@
 """Cross-check bench.py's live roofline timings against the rocprofv3 kernel trace of the same command.
 
-usage: python tools/roofline_check.py gpurun_out/prof/run_kernel_trace.csv [--n 20] [--bench gpurun_out/prof/bench.json]
+usage: python tools/roofline_check.py out/prof/run_kernel_trace.csv [--n 20] [--bench out/prof/bench.json]
+(the trace and the JSON line of one `bench.py --full` run under rocprofv3, e.g. tools/gpu_prof.sh)
 
 bench.py's conv_roofline() issues 3 warm-up + 20 timed launches of each roofline problem (8x256^2, 128 -> 128) after
 the train and sampler legs, so they are the LAST launches of their kernel at that grid in the trace:
