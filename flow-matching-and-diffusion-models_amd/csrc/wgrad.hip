@@ -31,15 +31,14 @@ struct WArgs {
 FMD_DEV int swz(int row) { return 4 * ((row & 3) | (((row >> 3) & 1) << 2)); }
 FMD_DEV int lds_off(int row, int unit) { return row * 128 + 4 * (unit ^ swz(row)); }  // in bf16 elements
 
-__global__ __launch_bounds__(256, 2) void wgrad_kernel(const WArgs A) {
+// bx = (co tile, tap, ci tile) index, split of nsplit: a single launch's blockIdx.x, blockIdx.y of gridDim.y
+FMD_DEV void wgrad_body(const WArgs& A, int bx, const int split, const int nsplit) {
   __shared__ __attribute__((aligned(16))) bf16r lds[2][2][BKP * 128];
   __shared__ float bsum[4][BCO];
   const fmd_wgrad_desc& d = A.d;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
 
-  // grid: x = (co tile, tap, ci tile), y = split
-  int bx = blockIdx.x;
   const int tco = bx % A.ntc; bx /= A.ntc;
   const int tci = bx % A.nci; bx /= A.nci;
   const int tap = bx;
@@ -55,7 +54,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WArgs A) {
   const int ky = t2 / d.ks, kx = t2 - (t2 / d.ks) * d.ks;
   const bool d3 = d.Do > 0;
   const int Dsz = d.Ds > 0 ? d.Ds : 1, Dz = d.Do > 0 ? d.Do : 1;
-  const int split = blockIdx.y;
   const int s0 = split * A.per_split;
   const int s1 = min(A.nsteps, s0 + A.per_split);
   const bool do_bias = d.db && tap == 0 && tci == 0;
@@ -238,10 +236,38 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WArgs A) {
     }
     __syncthreads();
     if (tid < BCO && co0 + tid < d.K) {
-      float* wb = d.ws + (size_t)gridDim.y * d.K * A.T * A.C + (size_t)split * d.K;
+      float* wb = d.ws + (size_t)nsplit * d.K * A.T * A.C + (size_t)split * d.K;
       wb[co0 + tid] = bsum[0][tid] + bsum[1][tid] + bsum[2][tid] + bsum[3][tid];
     }
   }
+}
+
+__global__ __launch_bounds__(256, 2) void wgrad_kernel(const WArgs A) {
+  wgrad_body(A, blockIdx.x, blockIdx.y, gridDim.y);   // grid: x = (co tile, tap, ci tile), y = split
+}
+
+// Grouped launches: job j owns blocks [start[j], start[j + 1]) of a 1-D grid; the table is a by-value kernel
+// argument (baked into a captured graph node).
+struct WGroup {
+  WArgs a[FMD_WGRAD_GROUP_MAX];
+  int gx[FMD_WGRAD_GROUP_MAX];       // blocks per split (a single launch's gridDim.x)
+  int nsplit[FMD_WGRAD_GROUP_MAX];
+  int start[FMD_WGRAD_GROUP_MAX + 1];
+  int n;
+};
+static_assert(sizeof(WGroup) <= 4096, "kernel arguments are limited to 4 KB: lower FMD_WGRAD_GROUP_MAX");
+
+FMD_DEV int group_job(const int* start, int n) {
+  int j = 0;
+  while (j + 1 < n && (int)blockIdx.x >= start[j + 1]) ++j;   // wave-uniform
+  return __builtin_amdgcn_readfirstlane(j);
+}
+
+__global__ __launch_bounds__(256, 2) void wgrad_group_kernel(const WGroup G) {
+  const int j = group_job(G.start, G.n);
+  const int local = (int)blockIdx.x - G.start[j];
+  const int split = local / G.gx[j];
+  wgrad_body(G.a[j], local - split * G.gx[j], split, G.nsplit[j]);
 }
 
 // Sum the split-K slabs ws[s*sstride][k][tap][c] (s < nsl) and write the reference layout dW[k][c][tap]
@@ -287,11 +313,12 @@ __global__ __launch_bounds__(256) void wgrad_reduce(const WArgs A, int splits, i
 // slabs sl, sl + SL, ... (of the nsl slabs at stride sstride) as 16-byte loads in four chains; the lanes are then
 // combined in fixed order through LDS and written transposed to the reference dW[k][c][tap] layout.
 // Deterministic.  T <= 27, C % 4 == 0, blockDim 512.
-__global__ __launch_bounds__(512) void wgrad_reduce2(const WArgs A, int splits, int nsl, int sstride, int SL) {
+// (k, cy): the block's output channel and 64-channel block (a single launch's blockIdx.x, blockIdx.y)
+FMD_DEV void wgrad_reduce2_body(const WArgs& A, int splits, int nsl, int sstride, int SL, const int k, const int cy) {
   const fmd_wgrad_desc& d = A.d;
   __shared__ __attribute__((aligned(16))) float part[512 * 4];   // [sl][tap][64 c]
   const size_t per = (size_t)d.K * A.T * A.C;
-  const int k = blockIdx.x, c0 = blockIdx.y * RC;
+  const int c0 = cy * RC;
   const int items = 16 * A.T;
   const int t = threadIdx.x;
   if (t < items * SL) {
@@ -323,7 +350,7 @@ __global__ __launch_bounds__(512) void wgrad_reduce2(const WArgs A, int splits, 
     for (int sl = 1; sl < SL; ++sl) v += part[((size_t)sl * A.T + tap) * 64 + cl];
     out[e] = d.accumulate ? out[e] + v : v;
   }
-  if (d.db && blockIdx.y == 0 && t < 64) {
+  if (d.db && cy == 0 && t < 64) {
     const float* wb = d.ws + (size_t)splits * per;
     float v = 0.f;
     for (int s = t; s < nsl; s += 64) v += wb[(size_t)s * sstride * d.K + k];
@@ -331,6 +358,60 @@ __global__ __launch_bounds__(512) void wgrad_reduce2(const WArgs A, int splits, 
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
     if (t == 0) d.db[k] = d.accumulate ? d.db[k] + v : v;
   }
+}
+
+__global__ __launch_bounds__(512) void wgrad_reduce2(const WArgs A, int splits, int nsl, int sstride, int SL) {
+  wgrad_reduce2_body(A, splits, nsl, sstride, SL, blockIdx.x, blockIdx.y);
+}
+
+// One slab (splits == 1, the small levels of a grouped launch): nothing to sum, the combine is the transpose to
+// dW[k][c][tap].  wgrad_reduce2 would load with 16 T of its 512 threads; here a block takes R = 32 / T output
+// channels at once (R * 16 T loading threads, the slab-lane dimension of the LDS image holding the rows).  Same
+// values as wgrad_reduce2 with one slab, bit for bit: v + 0 as its accumulators start from zero.
+FMD_DEV void wgrad_reduce_one_body(const WArgs& A, const int R, const int k0, const int cy) {
+  const fmd_wgrad_desc& d = A.d;
+  __shared__ __attribute__((aligned(16))) float rows[512 * 4];   // [row][tap][64 c], R * T <= 32
+  const size_t per = (size_t)d.K * A.T * A.C;
+  const int c0 = cy * RC, items = 16 * A.T, t = threadIdx.x;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  if (t < items * R) {
+    const int row = t / items, it = t - row * items;
+    const int tap = it >> 4, cq = it & 15;
+    const int c = c0 + cq * 4, k = k0 + row;
+    f32x4 v = zero;
+    if (c < A.C && k < d.K) v += *(const f32x4*)(d.ws + ((size_t)k * A.T + tap) * A.C + c);
+    *(f32x4*)&rows[((size_t)row * A.T + tap) * 64 + cq * 4] = v;
+  }
+  __syncthreads();
+  const int nc = min(RC, A.C - c0), pr = nc * A.T;
+  const int nr = min(R, d.K - k0);
+  for (int e = t; e < nr * pr; e += blockDim.x) {
+    const int row = e / pr, r = e - row * pr;
+    const int cl = r / A.T, tap = r - cl * A.T;
+    const float v = rows[((size_t)row * A.T + tap) * 64 + cl];
+    float* out = d.dw + ((size_t)(k0 + row) * A.C + c0) * A.T;
+    out[r] = d.accumulate ? out[r] + v : v;
+  }
+  if (d.db && cy == 0 && t < nr) {
+    const float v = 0.f + d.ws[per + k0 + t];
+    d.db[k0 + t] = d.accumulate ? d.db[k0 + t] + v : v;
+  }
+}
+
+// The combines of a group in one launch: job j's blocks are its (k, 64-channel block) pairs, k fastest
+// (splits == 1: (R-channel row block, 64-channel block) pairs; gx = R).
+__global__ __launch_bounds__(512) void wgrad_reduce2_group(const WGroup G) {
+  const int j = group_job(G.start, G.n);
+  const int local = (int)blockIdx.x - G.start[j];
+  const int K = G.a[j].d.K;
+  if (G.nsplit[j] == 1) {
+    const int R = G.gx[j], nkb = (K + R - 1) / R;
+    const int cy = local / nkb;
+    wgrad_reduce_one_body(G.a[j], R, (local - cy * nkb) * R, cy);
+    return;
+  }
+  const int cy = local / K;
+  wgrad_reduce2_body(G.a[j], G.nsplit[j], G.nsplit[j], 1, G.gx[j], local - cy * K, cy);   // gx = slab lanes
 }
 
 WArgs make_args(const fmd_wgrad_desc* d) {
@@ -359,11 +440,59 @@ extern "C" int64_t fmd_wgrad_workspace(const fmd_wgrad_desc* d) {
   return (int64_t)splits * d->K * T * C + (int64_t)splits * d->K;
 }
 
-extern "C" int fmd_wgrad(const fmd_wgrad_desc* d, fmd_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
+static int check_desc(const fmd_wgrad_desc* d) {
   if ((d->C0 % 8) || (d->C1 % 8) || (d->K % 8) || !d->ws || !d->dw) return -1;
   if (d->ldy > 0 && (d->ldy % 8)) return -3;
   if (d->C1 && !d->src1) return -2;
+  return 0;
+}
+
+extern "C" int fmd_wgrad_group(const fmd_wgrad_desc* descs, int32_t n, fmd_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n < 1 || n > FMD_WGRAD_GROUP_MAX) return -6;
+  WGroup G;
+  for (int j = 0; j < n; ++j) {
+    if (int rc = check_desc(descs + j)) return rc;
+    G.a[j] = make_args(descs + j);
+    if (G.a[j].T > 27) return -4;
+    G.nsplit[j] = descs[j].splits > 1 ? descs[j].splits : 1;
+  }
+  G.n = n;
+  int rc = fmd_wgrad_halo_group(descs, n, stream);   // -5: the jobs are not of one kernel instance
+  if (rc == 1) {   // none on the halo kernel (not applicable or force_generic): all on the generic kernel
+    int nwg = 0;
+    for (int j = 0; j < n; ++j) {
+      const WArgs& A = G.a[j];
+      G.gx[j] = A.ntc * (A.merged ? A.nci : A.nci * A.T);
+      G.start[j] = nwg;
+      nwg += G.gx[j] * G.nsplit[j];
+    }
+    for (int j = n; j <= FMD_WGRAD_GROUP_MAX; ++j) G.start[j] = nwg;
+    hipLaunchKernelGGL(wgrad_group_kernel, dim3(nwg), dim3(256), 0, s, G);
+    rc = (int)hipGetLastError();
+  }
+  if (rc) return rc;
+  int nblk = 0;
+  for (int j = 0; j < n; ++j) {
+    const WArgs& A = G.a[j];
+    const int lanes = 512 / (16 * A.T);   // >= 1 (T <= 27)
+    G.gx[j] = max(1, min(G.nsplit[j], lanes));   // slab lanes, as fmd_wgrad
+    G.start[j] = nblk;
+    int rows = A.d.K;
+    if (G.nsplit[j] == 1) {   // one slab: lanes output channels per block (wgrad_reduce_one_body)
+      G.gx[j] = lanes;
+      rows = (A.d.K + lanes - 1) / lanes;
+    }
+    nblk += rows * ((A.C + RC - 1) / RC);
+  }
+  for (int j = n; j <= FMD_WGRAD_GROUP_MAX; ++j) G.start[j] = nblk;
+  hipLaunchKernelGGL(wgrad_reduce2_group, dim3(nblk), dim3(512), 0, s, G);
+  return (int)hipGetLastError();
+}
+
+extern "C" int fmd_wgrad(const fmd_wgrad_desc* d, fmd_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = check_desc(d)) return rc;
   WArgs A = make_args(d);
   const int splits = d->splits > 1 ? d->splits : 1;
   int rc = d->force_generic ? 1 : fmd_wgrad_halo(d, stream);

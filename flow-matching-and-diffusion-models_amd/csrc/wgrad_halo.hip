@@ -27,6 +27,11 @@
 // 64-channel block) pair staging slice z + kz - 1 (zeros outside the sample, >> 1 under nearest-x2); its
 // 9 accumulated taps land at taps kz*9 .. kz*9+8 of a 27-tap slab, so wgrad_reduce writes [K][C][3][3][3].
 //
+// Grouped launch (fmd_wgrad_halo_group): alone, a problem needs ~one workgroup per CU whatever its size, i.e. ~256
+// slab tiles of 128 x 64 x 9 fp32 (75 MB written, and read back by the reduce) per launch.  The jobs of one UNet
+// level share a launch instead: a workgroup finds its job in a by-value table from blockIdx.x and runs the same
+// body on that job's arguments, so G jobs fill the chip with 1/G of the splits -- and of the slab bytes -- each.
+//
 // Replaces: autograd of nn.Conv2d weight/bias (src/nn/ops/convolution.py:53) for
 // the ResBlock 3x3 convs (src/nn/blocks/residual.py:71-76).
 #include "common.h"
@@ -69,8 +74,9 @@ struct HWArgs {
 template <int V> struct IC { static constexpr int value = V; };
 
 // PRO: 0 = raw input, 1 = GroupNorm affine, 2 = affine + SiLU; S2D: stride 2 (planes as chunks)
-template <int PRO, bool S2D = false>
-__global__ __launch_bounds__(512) void wgrad_halo_kernel(const HWArgs A) {
+// blk of nblk: this workgroup's index in its job's own block range (the whole grid of a single launch)
+template <int PRO, bool S2D>
+FMD_DEV void wgrad_halo_body(const HWArgs& A, const int blk, const int nblk) {
   __shared__ __attribute__((aligned(16))) bf16r lds[2 * XBUF + 2 * DBUF];
   bf16r* xb = lds;
   bf16r* db_ = lds + 2 * XBUF;
@@ -81,7 +87,7 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const HWArgs A) {
   const int l16 = lane & 15, lq = lane >> 4;
   const int rq = l16 >> 2, rp = lane & 3;          // transposed-read row / column group
 
-  int b = xcd_remap(blockIdx.x, gridDim.x);
+  int b = xcd_remap(blk, nblk);
   const int tci = b % A.nci; b /= A.nci;
   const int tco = b % A.ntc; b /= A.ntc;
   const int split = b;
@@ -333,12 +339,30 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const HWArgs A) {
   }
 }
 
-}  // namespace
+template <int PRO, bool S2D = false>
+__global__ __launch_bounds__(512) void wgrad_halo_kernel(const HWArgs A) {
+  wgrad_halo_body<PRO, S2D>(A, blockIdx.x, gridDim.x);
+}
 
-// 3x3 / stride 1 / pad 1 (optionally on the nearest-x2 upsample of src) or 2-D stride 2 / pad 1 (Hs = 2 Ho,
-// Ws = 2 Wo), K % 128 == 0, C % 64 == 0, Ho % 8 == 0, Wo % 16 == 0.
-// Returns 1 (nothing launched) when the problem does not qualify.  d->splits = pixel-tile splits.
-extern "C" int fmd_wgrad_halo(const fmd_wgrad_desc* d, fmd_stream_t stream) {
+// Grouped launch: the jobs of one level share the grid, job j owning blocks [start[j], start[j + 1]).  The table
+// travels by value in the kernel arguments (baked into a captured graph node; no device-side table to keep alive).
+struct HWGroup {
+  HWArgs a[FMD_WGRAD_GROUP_MAX];
+  int start[FMD_WGRAD_GROUP_MAX + 1];
+  int n;
+};
+static_assert(sizeof(HWGroup) <= 4096, "kernel arguments are limited to 4 KB: lower FMD_WGRAD_GROUP_MAX");
+
+template <int PRO, bool S2D>
+__global__ __launch_bounds__(512) void wgrad_halo_group_kernel(const HWGroup G) {
+  int j = 0;
+  while (j + 1 < G.n && (int)blockIdx.x >= G.start[j + 1]) ++j;   // wave-uniform
+  j = __builtin_amdgcn_readfirstlane(j);
+  wgrad_halo_body<PRO, S2D>(G.a[j], (int)blockIdx.x - G.start[j], G.start[j + 1] - G.start[j]);
+}
+
+// Kernel arguments of one problem; 1 when it does not qualify for the halo kernel.
+int halo_args(const fmd_wgrad_desc* d, HWArgs& A) {
   const bool s2 = d->stride == 2;   // S2D (2-D): the input's space-to-depth planes as chunks
   if (d->ks != 3 || (d->stride != 1 && !s2) || d->pad != 1 || (s2 && d->upsample)) return 1;
   const bool d3 = d->Do > 0 || d->Ds > 0;
@@ -352,7 +376,6 @@ extern "C" int fmd_wgrad_halo(const fmd_wgrad_desc* d, fmd_stream_t stream) {
   const int ldy = d->ldy > 0 ? d->ldy : d->K;
   if (ldy % 8) return 1;
   if ((long long)Nn * d->Hs * d->Ws >= (1LL << 31) / 8) return 1;
-  HWArgs A;
   A.d = *d;
   A.C = C;
   A.ldy = ldy;
@@ -371,6 +394,18 @@ extern "C" int fmd_wgrad_halo(const fmd_wgrad_desc* d, fmd_stream_t stream) {
 #else
   A.dbg = 0;
 #endif
+  return 0;
+}
+
+}  // namespace
+
+// 3x3 / stride 1 / pad 1 (optionally on the nearest-x2 upsample of src) or 2-D stride 2 / pad 1 (Hs = 2 Ho,
+// Ws = 2 Wo), K % 128 == 0, C % 64 == 0, Ho % 8 == 0, Wo % 16 == 0.
+// Returns 1 (nothing launched) when the problem does not qualify.  d->splits = pixel-tile splits.
+extern "C" int fmd_wgrad_halo(const fmd_wgrad_desc* d, fmd_stream_t stream) {
+  HWArgs A;
+  if (halo_args(d, A)) return 1;
+  const bool s2 = d->stride == 2;
   const int nwg = A.ntc * A.nci * A.splits;
   const int pro = d->pro_a ? (d->pro_silu ? 2 : 1) : 0;
   hipStream_t st = (hipStream_t)stream;
@@ -381,5 +416,39 @@ extern "C" int fmd_wgrad_halo(const fmd_wgrad_desc* d, fmd_stream_t stream) {
   } else if (pro == 2) hipLaunchKernelGGL(wgrad_halo_kernel<2>, dim3(nwg), dim3(NT), 0, st, A);
   else if (pro == 1) hipLaunchKernelGGL(wgrad_halo_kernel<1>, dim3(nwg), dim3(NT), 0, st, A);
   else hipLaunchKernelGGL(wgrad_halo_kernel<0>, dim3(nwg), dim3(NT), 0, st, A);
+  return (int)hipGetLastError();
+}
+
+// n <= FMD_WGRAD_GROUP_MAX halo problems of ONE kernel instance (same prologue form, same stride) in one launch:
+// each job runs exactly the workgroups, tiles and slab writes fmd_wgrad_halo gives it for its own ``splits``.
+// Returns 1 (nothing launched) when no job qualifies, -5 when only some do or the instances differ.
+extern "C" int fmd_wgrad_halo_group(const fmd_wgrad_desc* descs, int32_t n, fmd_stream_t stream) {
+  if (n < 1 || n > FMD_WGRAD_GROUP_MAX) return -6;
+  HWGroup G;
+  int nq = 0, nwg = 0, pro0 = 0;
+  bool s20 = false;
+  for (int j = 0; j < n; ++j) {
+    const fmd_wgrad_desc* d = descs + j;
+    if (d->force_generic || halo_args(d, G.a[j])) continue;
+    const int pro = d->pro_a ? (d->pro_silu ? 2 : 1) : 0;
+    const bool s2 = d->stride == 2;
+    if (nq == 0) { pro0 = pro; s20 = s2; }
+    else if (pro != pro0 || s2 != s20) return -5;
+    ++nq;
+    G.start[j] = nwg;
+    nwg += G.a[j].ntc * G.a[j].nci * G.a[j].splits;
+  }
+  if (nq == 0) return 1;
+  if (nq != n) return -5;
+  for (int j = n; j <= FMD_WGRAD_GROUP_MAX; ++j) G.start[j] = nwg;
+  G.n = n;
+  hipStream_t st = (hipStream_t)stream;
+  if (s20) {
+    if (pro0 == 2) hipLaunchKernelGGL((wgrad_halo_group_kernel<2, true>), dim3(nwg), dim3(NT), 0, st, G);
+    else if (pro0 == 1) hipLaunchKernelGGL((wgrad_halo_group_kernel<1, true>), dim3(nwg), dim3(NT), 0, st, G);
+    else hipLaunchKernelGGL((wgrad_halo_group_kernel<0, true>), dim3(nwg), dim3(NT), 0, st, G);
+  } else if (pro0 == 2) hipLaunchKernelGGL((wgrad_halo_group_kernel<2, false>), dim3(nwg), dim3(NT), 0, st, G);
+  else if (pro0 == 1) hipLaunchKernelGGL((wgrad_halo_group_kernel<1, false>), dim3(nwg), dim3(NT), 0, st, G);
+  else hipLaunchKernelGGL((wgrad_halo_group_kernel<0, false>), dim3(nwg), dim3(NT), 0, st, G);
   return (int)hipGetLastError();
 }

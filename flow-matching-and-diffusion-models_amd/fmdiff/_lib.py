@@ -105,6 +105,8 @@ SIGNATURES = {
     "fmd_wgrad": [C.POINTER(WgradDesc), p],
     "fmd_wgrad_workspace": [C.POINTER(WgradDesc)],
     "fmd_wgrad_halo": [C.POINTER(WgradDesc), p],
+    "fmd_wgrad_group": [C.POINTER(WgradDesc), i32, p],
+    "fmd_wgrad_halo_group": [C.POINTER(WgradDesc), i32, p],
     "fmd_halo_tiled_size": [i32, i32, i32],
     "fmd_tile_weights_halo": [p, i32, i32, i32, p, p],
     "fmd_conv_s2d": [C.POINTER(ConvDesc), p],

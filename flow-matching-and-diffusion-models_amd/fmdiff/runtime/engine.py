@@ -358,6 +358,7 @@ class UNetEngine:
         # spatial_dims = 1: signals run as (L, 1) images -- 1-D k-tap weights embedded as k x k
         # (WeightCache.embed1d), resampling along the first dim only
         self.dims1 = next(c for c in model.modules() if isinstance(c, Conv)).dims == 1
+        self._wq = ops.WgradQueue()   # weight gradients waiting for their level's grouped launch (_wg / _join)
 
     @staticmethod
     def _group_emb_layers(model):
@@ -419,7 +420,8 @@ class UNetEngine:
                 def wg():
                     tgt = self._wgrad_target(conv, Cin)
                     ops.wgrad(x.t, dy, tgt, ks=3, stride=stride, pad=1, upsample=upsample,
-                              db=conv.bias.grad if conv.bias is not None else None)
+                              db=conv.bias.grad if conv.bias is not None else None,
+                              immediate=tgt is not conv.weight.grad)
                     self._wgrad_finish(conv, Cin, tgt)
                 self._wg(wg, dy.numel() // dy.shape[-1])
                 if not x.need_grad:
@@ -470,7 +472,8 @@ class UNetEngine:
                 def wg():
                     tgt = self._wgrad_target(conv, Cin)
                     ops.wgrad(x.t, o.grad, tgt, ks=pf, stride=pf, pad=0,
-                              db=conv.bias.grad if conv.bias is not None else None)
+                              db=conv.bias.grad if conv.bias is not None else None,
+                              immediate=tgt is not conv.weight.grad)
                     self._wgrad_finish(conv, Cin, tgt)
                 self._wg(wg)
             ctx.tape.append(bwd)
@@ -496,7 +499,7 @@ class UNetEngine:
             def bwd(dpred):
                 def wg():
                     tmp = torch.zeros((mc, Kp, *ct.kernel_size), device=hb.device, dtype=F32)
-                    ops.wgrad(dpred, hb, tmp, ks=pf, stride=pf, pad=0, accumulate=False)
+                    ops.wgrad(dpred, hb, tmp, ks=pf, stride=pf, pad=0, accumulate=False, immediate=True)
                     ct.weight.grad.add_(tmp[:, :K])
                     if ct.bias is not None:
                         ct.bias.grad.add_(ops.channel_stats(dpred).slab[..., 0].sum(0)[:K])
@@ -530,11 +533,23 @@ class UNetEngine:
     def _wg(self, fn, px=None):
         """Weight-gradient work, issued in line on the current stream.  (A side-stream variant beside the
         data-gradient chain measured no gain on MI355X -- the halo wgrad / dgrad kernels contend for LDS and
-        the issue port -- and was retired in round 4.)"""
-        fn()
+        the issue port -- and was retired in round 4.)
+
+        With WGRAD_GROUP the ops.wgrad calls of ``fn`` that can wait are queued (ops.WgradQueue) and leave as one
+        grouped launch per level and kernel instance: nothing reads a weight gradient before ``_join``.  The queue
+        holds every operand tensor until its launch, and no operand is written in between: an activation gradient
+        is complete before its producer's backward enqueues it (all consumers ran earlier on the tape), dh and the
+        materialised operands are fresh tensors written once, and the forward activations / GroupNorm affines are
+        read-only during the backward.  Calls that post-process their dW at once pass ``immediate=True``."""
+        if not ops.WGRAD_GROUP:
+            fn()
+            return
+        with ops.wgrad_defer(self._wq):
+            fn()
 
     def _join(self):
-        pass
+        """Weight gradients are final: launch whatever is still queued."""
+        self._wq.flush()
 
     def _wts(self, w, mode, halo: bool, Kpad=None, Cpad=None):
         """(base, tiled) kernel layouts of ``w``: only the one the chosen conv path reads is derived
@@ -987,7 +1002,7 @@ class UNetEngine:
                     Ki = w_.shape[0]
                     tgt = w_.grad if w_.shape[1] == Cp else torch.zeros((Ki, Cp, *w_.shape[2:]), device=w_.device,
                                                                        dtype=F32)
-                    ops.wgrad(cn, dkv, tgt, ks=1, pad=0, db=b_.grad, dy_offset=off)
+                    ops.wgrad(cn, dkv, tgt, ks=1, pad=0, db=b_.grad, dy_offset=off, immediate=tgt is not w_.grad)
                     if tgt is not w_.grad:
                         w_.grad.add_(tgt[:, :m.context_dim])
                     off += Ki
@@ -1035,7 +1050,7 @@ class UNetEngine:
                 def wgh():
                     tmpw = torch.zeros((Kp, Cc, *conv.weight.shape[2:]), device=out.device, dtype=F32)
                     tmpb = torch.zeros((Kp,), device=out.device, dtype=F32)
-                    ops.wgrad(h.t, dpred, tmpw, pro=(a, b, True), db=tmpb, accumulate=False)
+                    ops.wgrad(h.t, dpred, tmpw, pro=(a, b, True), db=tmpb, accumulate=False, immediate=True)
                     conv.weight.grad.add_(tmpw[:K])
                     conv.bias.grad.add_(tmpb[:K])
                 self._wg(wgh)
@@ -1283,6 +1298,13 @@ class UNetEngine:
                 a, b = ranges[k]
                 for fn in reversed(ctx.tape[a:b]):
                     fn()
+                # queued weight gradients never cross a segment: a job's splits depend on its group, so the
+                # groups must be the same however the segments are dealt to backward() calls (the per-bucket
+                # captured form is bit-equal to the single graph)
+                self._join()
+        except BaseException:
+            self._wq.clear()   # a failed backward leaves no weight gradient queued for the next one
+            raise
         finally:
             ops.gb_flush()
         self._join()   # every weight gradient of these segments has landed before anyone reads .grad

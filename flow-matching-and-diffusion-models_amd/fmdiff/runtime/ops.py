@@ -13,7 +13,7 @@ from typing import Optional, Tuple
 import torch
 
 from .. import _lib
-from . import tuning
+from . import tuning, wgrad_plan
 from .._lib import ConvDesc, GnApplyDesc, GnOutDesc, WgradDesc
 
 BF16 = torch.bfloat16
@@ -794,6 +794,10 @@ WGRAD_HALO_WG = tuning.get("WGRAD_HALO_WG") or NUM_CU
 WGRAD_SLAB_MB = tuning.get("WGRAD_SLAB_MB")
 WGRAD_GEN_SLAB_MB = tuning.get("WGRAD_GEN_SLAB_MB")
 WGRAD_S2D = bool(tuning.get("WGRAD_S2D"))
+# grouped weight gradients (fmd_wgrad_group): the deferred jobs of a level in one launch with the group's splits
+WGRAD_GROUP = bool(tuning.get("WGRAD_GROUP"))
+WGRAD_GROUP_MAX_PIX = tuning.get("WGRAD_GROUP_MAX_PIX")
+WGRAD_GROUP_SPLITS = tuning.get("WGRAD_GROUP_SPLITS")
 
 
 def wgrad_halo_eligible(Hs, Ws, Ho, Wo, K, C, C0, ks=3, stride=1, pad=1, upsample=False, ldy=None) -> bool:
@@ -807,23 +811,26 @@ def wgrad_halo_eligible(Hs, Ws, Ho, Wo, K, C, C0, ks=3, stride=1, pad=1, upsampl
             and Wo % 16 == 0 and K % 128 == 0 and C % 64 == 0 and C0 % 8 == 0 and (ldy or K) % 8 == 0)
 
 
-def wgrad(src0, dy, dw, *, src1=None, ks=3, stride=1, pad=1, upsample=False, pro=None, db=None, accumulate=True,
-          splits=None, dy_offset=0, force_generic=False):
-    """dW (+)= conv weight gradient in the reference [K][C][kh][kw] fp32 layout (and db).
+def _plan_kw() -> dict:
+    return dict(num_cu=NUM_CU, halo_wg=WGRAD_HALO_WG, slab_mb=WGRAD_SLAB_MB, gen_slab_mb=WGRAD_GEN_SLAB_MB,
+                min_steps=WGRAD_MIN_STEPS, cu_mult=WGRAD_CU_MULT)
 
-    ``dy_offset``: use channels [dy_offset, dy_offset + dw.shape[0]) of a wider dY (fused q/k/v).
-    A 1-D k-tap weight ([K][C][k], k > 1) on (L, 1)-image activations: the k x k gradient of its embedding
-    is computed and its centre column (the only one that meets data) is added in."""
-    if dw.dim() == 3 and dw.shape[2] > 1 and src0.dim() == 4:
-        full = torch.zeros((*dw.shape[:2], ks, ks), device=dw.device, dtype=F32)
-        wgrad(src0, dy, full, src1=src1, ks=ks, stride=stride, pad=pad, upsample=upsample, pro=pro, db=db,
-              accumulate=accumulate, splits=splits, dy_offset=dy_offset, force_generic=force_generic)
-        col = full[..., (ks - 1) // 2]
-        if accumulate:
-            dw.add_(col)
-        else:
-            dw.copy_(col)
-        return
+
+class WgradJob:
+    """One weight gradient ready to launch but for its splits and workspace: the descriptor, its shape record
+    for the planner and the tensors the descriptor points into (kept alive until the launch is issued)."""
+    __slots__ = ("d", "shape", "keep", "device")
+
+    def __init__(self, d, shape, keep, device):
+        self.d, self.shape, self.keep, self.device = d, shape, keep, device
+
+    def single_splits(self) -> int:
+        return wgrad_plan.single_splits(self.shape, **_plan_kw())
+
+
+def wgrad_job(src0, dy, dw, *, src1=None, ks=3, stride=1, pad=1, upsample=False, pro=None, db=None, accumulate=True,
+              dy_offset=0, force_generic=False) -> WgradJob:
+    """Descriptor of one weight gradient (arguments as for ``wgrad``); nothing is launched."""
     d3 = src0.dim() == 5
     if d3:
         N, Ds, Hs, Ws, C0 = src0.shape
@@ -845,29 +852,134 @@ def wgrad(src0, dy, dw, *, src1=None, ks=3, stride=1, pad=1, upsample=False, pro
         d.pro_a, d.pro_b, d.pro_silu = _p(pro[0]), _p(pro[1]), int(pro[2])
     d.dy, d.ldy, d.dw, d.db, d.accumulate = dy.data_ptr() + 2 * dy_offset, ldy, _p(dw), _p(db), int(accumulate)
     d.force_generic = int(force_generic)
-    if splits is None:
-        if (not force_generic and (not d3 or (stride == 1 and Do == (2 * Ds if upsample else Ds))) and
-                wgrad_halo_eligible(Hs, Ws, Ho, Wo, K, Ct, C0, ks, stride, pad, upsample, ldy)):
-            # halo kernel: one workgroup per CU over (cout tile, 64-cin chunk [x depth tap | x stride-2 plane],
-            # pixel-tile split); partial slabs capped at ~96 MB (their write + reduce read)
-            zt = 3 if d3 else 1
-            tiles = N * max(Do, 1) * (Ho // 8) * (Wo // 16)
-            base = (K // 128) * (Ct // 64) * zt * (4 if stride == 2 else 1)
-            splits = max(1, min(tiles, -(-WGRAD_HALO_WG // base), (WGRAD_SLAB_MB << 20) // (K * Ct * 36 * zt)))
+    # the kernel the library will choose (mirror of fmd_wgrad's dispatch) and the shape the split rules work on:
+    # halo kernel -- workgroups over (cout tile, 64-cin chunk [x depth tap | x stride-2 plane], pixel-tile split);
+    # generic kernel -- narrow inputs (Ct < 128, T > 1) tile the flattened (tap, cin) pairs (csrc/wgrad.hip
+    # make_args ``merged``).  The rules themselves are in wgrad_plan.
+    halo = (not force_generic and (not d3 or (stride == 1 and Do == (2 * Ds if upsample else Ds))) and
+            wgrad_halo_eligible(Hs, Ws, Ho, Wo, K, Ct, C0, ks, stride, pad, upsample, ldy))
+    shape = wgrad_plan.Shape(N=N, Ho=Ho, Wo=Wo, K=K, C=Ct, ks=ks, stride=stride, halo=bool(halo),
+                             pro=0 if pro is None else 2 if pro[2] else 1, Do=Do)
+    keep = (src0, src1, dy, dw, db) + (tuple(pro[:2]) if pro is not None else ())
+    return WgradJob(d, shape, keep, dy.device)
+
+
+def _wgrad_workspace(jobs) -> torch.Tensor:
+    """One allocation for the jobs' partial slabs (each desc's ``splits`` set): d.ws of every job points into it."""
+    sizes = [-(-int(_lib.lib().fmd_wgrad_workspace(C.byref(j.d))) // 64) * 64 for j in jobs]
+    ws = torch.empty((sum(sizes),), device=jobs[0].device, dtype=F32)
+    off = 0
+    for j, n in zip(jobs, sizes):
+        j.d.ws = ws.data_ptr() + 4 * off
+        off += n
+    return ws
+
+
+def wgrad_group(jobs, splits) -> None:
+    """Launch the jobs (one kernel instance: equal ``shape.key``) with the given splits (an int for all, or one
+    per job) through fmd_wgrad_group: one MFMA launch and one combine launch per FMD_WGRAD_GROUP_MAX jobs.  Each
+    job's result is bit-identical to ``wgrad`` with the same splits."""
+    splits = [splits] * len(jobs) if isinstance(splits, int) else list(splits)
+    for lo in range(0, len(jobs), wgrad_plan.GROUP_MAX):
+        part = jobs[lo:lo + wgrad_plan.GROUP_MAX]
+        for j, s in zip(part, splits[lo:]):
+            j.d.splits = s
+        ws = _wgrad_workspace(part)   # noqa: F841 -- stream-ordered allocation: alive until the launches are issued
+        arr = (WgradDesc * len(part))(*[j.d for j in part])
+        _lib.call("fmd_wgrad_group", arr, len(part), stream())
+
+
+class WgradQueue:
+    """Deferred weight gradients of one backward pass, one list per kernel instance.  Nothing reads a weight
+    gradient before the engine's ``_join``, so the jobs of a level wait here and go out as grouped launches with
+    the group plan's (fewer) splits: when the output grid changes, when a list reaches the group cap, and at
+    ``flush``.  A job that would write a dW / db already queued flushes first (program order per destination)."""
+
+    def __init__(self):
+        self.lists = {}
+        self.grid = None
+        self.dests = set()
+
+    def __len__(self):
+        return sum(len(v) for v in self.lists.values())
+
+    def push(self, job: WgradJob) -> None:
+        dst = {int(job.d.dw or 0), int(job.d.db or 0)} - {0}
+        if (self.grid is not None and job.shape.grid != self.grid) or (dst & self.dests):
+            self.flush()
+        self.grid = job.shape.grid
+        self.dests |= dst
+        lst = self.lists.setdefault(job.shape.key, [])
+        lst.append(job)
+        if len(lst) >= wgrad_plan.GROUP_MAX:
+            self._launch(self.lists.pop(job.shape.key))
+
+    def _launch(self, jobs) -> None:
+        if WGRAD_GROUP_SPLITS:   # each job's ungrouped splits: bit-identical to the immediate path
+            wgrad_group(jobs, [j.single_splits() for j in jobs])
+            return
+        for idx, splits in wgrad_plan.plan_groups([j.shape for j in jobs], **_plan_kw()):
+            wgrad_group([jobs[i] for i in idx], splits)
+
+    def flush(self) -> None:
+        lists, self.lists, self.grid, self.dests = self.lists, {}, None, set()
+        for jobs in lists.values():
+            self._launch(jobs)
+
+    def clear(self) -> None:
+        self.lists, self.grid, self.dests = {}, None, set()
+
+
+_wgrad_queue: Optional[WgradQueue] = None
+
+
+class wgrad_defer:
+    """Within the block, ``wgrad`` calls that may wait are queued on ``queue`` instead of launched."""
+
+    def __init__(self, queue: Optional[WgradQueue]):
+        self.queue = queue
+
+    def __enter__(self):
+        global _wgrad_queue
+        self.prev, _wgrad_queue = _wgrad_queue, self.queue
+
+    def __exit__(self, *exc):
+        global _wgrad_queue
+        _wgrad_queue = self.prev
+
+
+def wgrad(src0, dy, dw, *, src1=None, ks=3, stride=1, pad=1, upsample=False, pro=None, db=None, accumulate=True,
+          splits=None, dy_offset=0, force_generic=False, immediate=False):
+    """dW (+)= conv weight gradient in the reference [K][C][kh][kw] fp32 layout (and db).
+
+    ``dy_offset``: use channels [dy_offset, dy_offset + dw.shape[0]) of a wider dY (fused q/k/v).
+    A 1-D k-tap weight ([K][C][k], k > 1) on (L, 1)-image activations: the k x k gradient of its embedding
+    is computed and its centre column (the only one that meets data) is added in.
+    Under ``wgrad_defer`` the job is queued for a grouped launch unless ``immediate`` (the caller post-processes
+    dw right away), ``splits`` is given, it is 3-D, or its output grid exceeds WGRAD_GROUP_MAX_PIX pixels; a job
+    launched at once flushes the queue first, so launches that write gradients keep their program order."""
+    q = _wgrad_queue
+    if dw.dim() == 3 and dw.shape[2] > 1 and src0.dim() == 4:
+        full = torch.zeros((*dw.shape[:2], ks, ks), device=dw.device, dtype=F32)
+        wgrad(src0, dy, full, src1=src1, ks=ks, stride=stride, pad=pad, upsample=upsample, pro=pro, db=db,
+              accumulate=accumulate, splits=splits, dy_offset=dy_offset, force_generic=force_generic, immediate=True)
+        col = full[..., (ks - 1) // 2]
+        if accumulate:
+            dw.add_(col)
         else:
-            # narrow inputs (Ct < 128, T > 1) tile the flattened (tap, cin) pairs (csrc/wgrad.hip make_args
-            # ``merged``): ceil(T * Ct / 128) column tiles -- the 3-D stem's 27 x 8 is 2 tiles, not 27
-            T = ks * ks * (ks if d3 else 1)
-            tiles = -(-K // 128) * (-(-(T * Ct) // 128) if T > 1 and Ct < 128 else -(-Ct // 128) * T)
-            steps = -(-M // 32)
-            # up to WGRAD_CU_MULT workgroups per CU (the kernel is latency-bound at one), >= WGRAD_MIN_STEPS
-            # 32-pixel steps per split, partial slabs <= 48 MB
-            cap = max(256, min(1024, (WGRAD_GEN_SLAB_MB << 20) // (K * Ct * T * 4)))
-            splits = max(1, min(steps // WGRAD_MIN_STEPS, -(-WGRAD_CU_MULT * NUM_CU // tiles), cap))
-    d.splits = splits
-    ws = torch.empty((int(_lib.lib().fmd_wgrad_workspace(C.byref(d))),), device=dy.device, dtype=F32)
-    d.ws = _p(ws)
-    _lib.call("fmd_wgrad", C.byref(d), stream())
+            dw.copy_(col)
+        return
+    job = wgrad_job(src0, dy, dw, src1=src1, ks=ks, stride=stride, pad=pad, upsample=upsample, pro=pro, db=db,
+                    accumulate=accumulate, dy_offset=dy_offset, force_generic=force_generic)
+    if q is not None:
+        if (not immediate and splits is None and src0.dim() == 4
+                and job.shape.pixels <= WGRAD_GROUP_MAX_PIX):
+            q.push(job)
+            return
+        q.flush()
+    job.d.splits = job.single_splits() if splits is None else splits
+    ws = _wgrad_workspace([job])   # noqa: F841
+    _lib.call("fmd_wgrad", C.byref(job.d), stream())
 
 
 def prep_weights(w: torch.Tensor, mode: int, Kpad: Optional[int] = None, Cpad: Optional[int] = None, out=None):

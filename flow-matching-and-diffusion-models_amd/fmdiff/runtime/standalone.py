@@ -65,6 +65,7 @@ def _block_engine_cls():
             self.gl, self.gl_slot = None, {}
             self._head_bwd = None
             self.dims1 = False
+            self._wq = ops.WgradQueue()
 
     return BlockEngine
 
@@ -121,6 +122,9 @@ class _BlockFunction(torch.autograd.Function):
         try:
             for fn in reversed(ctx.tape):
                 fn()
+        except BaseException:
+            eng._wq.clear()   # a failed backward leaves no weight gradient queued for the next one
+            raise
         finally:
             ops.gb_flush()
         eng._join()

@@ -57,6 +57,14 @@ TABLE = {
     "WGRAD_HALO_WG": (0, "halo weight gradient: target workgroups (0 = one per CU)"),
     "WGRAD_SLAB_MB": (96, "halo weight gradient: split-K slab cap (MB)"),
     "WGRAD_GEN_SLAB_MB": (48, "generic weight gradient: split-K slab cap (MB)"),
+    "WGRAD_GROUP": (1, "the engine defers a level's weight gradients and runs them as grouped launches "
+                       "(fmd_wgrad_group) with the group plan's splits (0: each at once, alone)"),
+    "WGRAD_GROUP_MAX_PIX": (131072, "... only on output grids of at most this many pixels (N x H x W; config B: "
+                                    "the 128^2 level and below); larger levels run each weight gradient at once, "
+                                    "its operands still in the Infinity Cache (DESIGN.md round 7: the 256^2 level "
+                                    "measured no gain grouped)"),
+    "WGRAD_GROUP_SPLITS": (0, "grouped weight gradients: 0 = the group plan's splits, 1 = every job's own ungrouped "
+                              "splits (bit-identical to WGRAD_GROUP=0; parity bisection)"),
 }
 
 # the per-switch environment variables this table replaced in round 5 (and earlier retired switches): setting one

@@ -34,6 +34,7 @@ class VAEEngine(UNetEngine):
         self._fold_key = None
         self._head_bwd = None
         self.dims1 = False   # the VAE engine runs 2-D models only (spatial_dims checked on entry)
+        self._wq = ops.WgradQueue()   # forward only: stays empty
 
     def _ctx(self, part, N, dev):
         emb = None

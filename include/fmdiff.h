@@ -308,6 +308,17 @@ int fmd_wgrad(const fmd_wgrad_desc* d, fmd_stream_t s);
 int fmd_wgrad_halo(const fmd_wgrad_desc* d, fmd_stream_t s);
 int64_t fmd_wgrad_workspace(const fmd_wgrad_desc* d);
 
+/* Grouped weight gradients: the n <= FMD_WGRAD_GROUP_MAX problems run as ONE MFMA launch and ONE combine
+ * launch.  Each desc keeps its own ws / splits / dw / db / accumulate exactly as for fmd_wgrad, and each job's
+ * arithmetic and summation order are those of fmd_wgrad with the same splits (bit-identical results).  All
+ * jobs must use the same kernel instance -- the halo kernel with the same prologue form and stride, or all
+ * the generic kernel -- otherwise a negative code is returned and nothing is launched.  The job table
+ * travels by value in the kernel arguments, so the call is safe under stream capture. */
+#define FMD_WGRAD_GROUP_MAX 16
+int fmd_wgrad_group(const fmd_wgrad_desc* descs, int32_t n, fmd_stream_t s);
+/* The halo launch of a group alone (partial slabs only, no reduce); 1 when no job qualifies. */
+int fmd_wgrad_halo_group(const fmd_wgrad_desc* descs, int32_t n, fmd_stream_t s);
+
 /* ------------------------------------------------------------- groupnorm
  * nn.GroupNorm (src/nn/ops/normalization.py:11-19, attention.py:97) is never
  * materialised: producers emit per-channel sums, fmd_gn_prep folds mean/rstd,
