@@ -15,8 +15,7 @@
 // the 1x1 skip conv + residual add (residual.py:77-82,120), and their autograd
 // data gradients (transposed gather).
 #include <cstdlib>
-#include "common.h"
-#include "../../include/fmdiff.h"
+#include "halo_args.h"
 
 namespace {
 
@@ -870,16 +869,36 @@ __global__ __launch_bounds__(CGN_NT) void combine_gn_kernel(const fmd_conv_desc 
   }
 }
 
-template <int BCO, int BPX, int WM, int WN, int BK, bool GNA = false>
-int launch(const fmd_conv_desc* d, hipStream_t s, const fmd_gn_apply_desc* g = nullptr) {
-  KArgs A;
+// The implicit-GEMM instances: cout tile, pixel tile, waves across the pixel tile, channels per K-iteration.
+struct Igemm {
+  int bco, bpx, wn, bk;
+  bool gna;
+  void (*kernel)(const KArgs);
+};
+const Igemm IG_K16 = {16, 256, 4, 64, false, conv_igemm<16, 256, 1, 4, 64>};
+const Igemm IG_K64 = {64, 128, 2, 64, false, conv_igemm<64, 128, 2, 2, 64>};
+const Igemm IG_PX32 = {128, 32, 2, 64, false, conv_igemm<128, 32, 2, 2, 64>};
+const Igemm IG_PX64 = {128, 64, 2, 64, false, conv_igemm<128, 64, 2, 2, 64>};
+const Igemm IG_PX128 = {128, 128, 2, 64, false, conv_igemm<128, 128, 2, 2, 64>};
+// BK = 32: a 32 KiB LDS footprint keeps 4-5 of these memory-bound workgroups per CU in flight
+const Igemm IG_GNA64 = {64, 128, 2, 32, true, conv_igemm<64, 128, 2, 2, 32, true>};
+const Igemm IG_GNA128 = {128, 128, 2, 32, true, conv_igemm<128, 128, 2, 2, 32, true>};
+
+// One instance's decision, host arithmetic only: the launch arguments of d in form f in *Ap.  Returns 0, -14 (the
+// instance cannot combine this split inside the launch) or -11 (it cannot emit the statistics).
+int igemm_decide(const Igemm& I, const fmd_conv_desc* d, const ConvForm& f, KArgs* Ap,
+                 const fmd_gn_apply_desc* g = nullptr) {
+  KArgs& A = *Ap;
+  const int BCO = I.bco, BPX = I.bpx, BK = I.bk;
   A.d = *d;
+  if (!f.tk) A.d.tickets = nullptr;
+  if (!f.stats) A.d.stats = nullptr;
   if (g) A.g = *g;
   const int Dz = d->Do > 0 ? d->Do : 1;
   A.M = d->N * Dz * d->Ho * d->Wo;
   A.T = d->ks * d->ks * (d->Do > 0 ? d->ks : 1);
   A.C = d->C0 + d->C1;
-  A.pack = A.C == 8 && BK >= 16 && !GNA;
+  A.pack = A.C == 8 && BK >= 16 && !I.gna;
   A.nk1 = A.pack ? (A.T + BK / 8 - 1) / (BK / 8) : ((A.C + BK - 1) / BK) * A.T;
   A.nk = A.nk1 + (d->src2 ? (d->C2 + d->C3 + BK - 1) / BK : 0);
   const int splits = d->splits > 1 ? d->splits : 1;
@@ -888,89 +907,166 @@ int launch(const fmd_conv_desc* d, hipStream_t s, const fmd_gn_apply_desc* g = n
   // parity classes; with fused statistics every class must tile its images by whole 64-pixel rows
   const int HWq = (d->Do > 0 ? d->Do / 2 : 1) * (d->Ho / 2) * (d->Wo / 2);
   A.par = d->transposed && d->stride == 2 && d->ks == 3 && d->pad == 1 && !(d->Ho & 1) && !(d->Wo & 1) &&
-          !(d->Do & 1) && (!d->stats || (HWq % 64 == 0 && (d->N * HWq) % BPX == 0)) && !d->src2 && !GNA && !A.pack;
+          !(d->Do & 1) && (!f.stats || (HWq % 64 == 0 && (d->N * HWq) % BPX == 0)) && !d->src2 && !I.gna && !A.pack;
   if (A.par) A.M = d->N * (d->Do > 0 ? d->Do / 2 : 1) * (d->Ho / 2) * (d->Wo / 2);   // pixels per parity class
   A.ntp = (A.M + BPX - 1) / BPX;
   A.ntc = (d->K + BCO - 1) / BCO;
   A.stats_rows = 64;
-  // split-K combined inside the launch (d->tickets): whole tiles, no parity classes; the statistics then come from the
+  // split-K combined inside the launch (f.tk): 2-D, whole tiles, no parity classes; the statistics then come from the
   // unsplit epilogue with one row per wave's pixel range (BPX / WN pixels)
-  const bool tk = splits > 1 && d->tickets;
-  if (tk && (GNA || A.par || A.M % BPX || d->K % BCO || d->out_f32 || d->accumulate ||
-             d->n_tickets < A.ntp * A.ntc))
+  if (f.tk && (I.gna || d->Do > 0 || A.par || A.M % BPX || d->K % BCO || d->out_f32 || d->accumulate ||
+               d->n_tickets < A.ntp * A.ntc))
     return -14;
-  if (d->stats) {
+  if (f.stats) {
     // every wave's pixel range must be one image and full
-    const int wrows = BPX / WN;
-    if (tk) {
-      if ((Dz * d->Ho * d->Wo) % wrows != 0 || d->tickets_rows != wrows) return -14;
+    const int wrows = BPX / I.wn;
+    if (f.tk) {
+      if ((Dz * d->Ho * d->Wo) % wrows != 0) return -14;
       A.stats_rows = wrows;
     } else if (wrows != 64 || (Dz * d->Ho * d->Wo) % 64 != 0 || A.M % BPX != 0 || splits > 1 || (A.par && HWq % 64)) {
       return -11;
     }
   }
-  dim3 grid(A.ntp * A.ntc, splits, A.par ? (d->Do > 0 ? 8 : 4) : 1);
-  hipLaunchKernelGGL((conv_igemm<BCO, BPX, WM, WN, BK, GNA>), grid, dim3(256), 0, s, A);
+  return 0;
+}
+
+int igemm_go(const Igemm& I, const KArgs& A, hipStream_t s) {
+  const int splits = A.d.splits > 1 ? A.d.splits : 1;
+  dim3 grid(A.ntp * A.ntc, splits, A.par ? (A.d.Do > 0 ? 8 : 4) : 1);
+  hipLaunchKernelGGL(I.kernel, grid, dim3(256), 0, s, A);
   return (int)hipGetLastError();
 }
 
-}  // namespace
+// The split-K combine launch: the statistics' FMD_SPLIT_STATS_ROWS-pixel rows where the problem tiles by them.
+bool combine_rows_ok(const fmd_conv_desc* d) {
+  const int HWo = (d->Do > 0 ? d->Do : 1) * d->Ho * d->Wo;
+  return d->K % 4 == 0 && (d->N * HWo) % FMD_SPLIT_STATS_ROWS == 0 && HWo % FMD_SPLIT_STATS_ROWS == 0;
+}
 
-// combine = false: the split-K partial slabs only (fmd_conv_gn runs its own combine)
-static int conv_run(const fmd_conv_desc* d, fmd_stream_t stream, bool combine) {
-  hipStream_t s = (hipStream_t)stream;
-  // largest output (pixels) run on 64- / 32-pixel tiles when split-K (mirrored by ops.BPX64_M / BPX32_M)
-  constexpr int small_m = 2048, tiny_m = 128;
-  const int C = d->C0 + d->C1;
+int combine_go(const fmd_conv_desc* d, hipStream_t s) {
+  const int M = d->N * (d->Do > 0 ? d->Do : 1) * d->Ho * d->Wo;
+  if (combine_rows_ok(d)) {
+    hipLaunchKernelGGL(splitk_reduce_rows, dim3(M / FMD_SPLIT_STATS_ROWS, (d->K + 63) / 64), dim3(256), 0, s, *d, M);
+  } else {
+    const size_t total = (size_t)M * d->K;
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(splitk_reduce, dim3(blocks), dim3(256), 0, s, *d, M);
+  }
+  return (int)hipGetLastError();
+}
+
+// What conv_decide settles and conv_go launches: the plan and the launch arguments of the kernel it names.
+struct Decision {
+  fmd_conv_plan_t p;
+  const Igemm* ig;
+  KArgs K;
+  HArgs H;
+};
+
+// The whole dispatch of fmd_conv, host arithmetic only (no HIP call; reads d's scalars and which of its pointers
+// are set).  The caller's offers -- the ticket and the statistics in allow, d->fold_* -- are taken where a kernel
+// takes them and dropped otherwise, the ticket before the fold; p.stats_rows says whether and how the launch writes the
+// statistics.  combine = false: the split-K partial slabs only (fmd_conv_gn runs its own combine).  Returns 0 or the
+// negative code of a descriptor that cannot run at all.
+int conv_decide(const fmd_conv_desc* d, int allow, bool combine, Decision* D) {
+  fmd_conv_plan_t& p = D->p;
+  p = fmd_conv_plan_t{};
   if ((d->C0 % 8) || (d->C1 % 8) || (d->C2 % 8) || (d->C3 % 8) || d->ks < 1 || d->N < 1) return -1;
   if (d->C3 && !d->src3) return -6;
   if (d->C1 && !d->src1) return -2;
   if (d->src2 && !d->wgt2 && !d->wgt2_tiled) return -3;
   if (d->pro_a && !d->pro_b) return -4;
   if (d->gout && !d->pro_a) return -9;
+  const bool split = d->splits > 1;
+  if (split && !d->ws) return -5;
   const int M = d->N * (d->Do > 0 ? d->Do : 1) * d->Ho * d->Wo;
-  const int HWo = (d->Do > 0 ? d->Do : 1) * d->Ho * d->Wo;
-  // split-K: the combine kernel produces the channel statistics (16-pixel rows) instead of the main kernel
-  const bool rows_ok = d->K % 4 == 0 && M % FMD_SPLIT_STATS_ROWS == 0 && HWo % FMD_SPLIT_STATS_ROWS == 0;
-  if (d->splits > 1 && (!d->ws || (d->stats && (!rows_ok || d->out_f32 || d->accumulate)))) return -5;
-  (void)C;
-  fmd_conv_desc dm = *d;
-  const bool tk = d->splits > 1 && d->tickets && combine;   // split-K combined inside the launch
-  if (!tk) dm.tickets = nullptr;
-  if (d->splits > 1 && !tk) dm.stats = nullptr;
-  int rc = 1;
-  if (d->K > 16 && !d->force_generic)
-    rc = fmd_conv_halo(&dm, stream);   // 3x3 stride-1 problems with >= HALO_MIN_WG (32) workgroups of 16x16 tiles (x splits)
-  if (rc == 1 && d->fold_st0) return -13;   // the in-kernel GroupNorm fold runs only on the halo kernel
-  // a ticketed problem the halo kernel declined runs ticketed on the implicit GEMM, or not at all (-14: the caller
-  // splits the two-launch way; the statistics' row size differs)
-  if (rc == 1 && tk && (!d->wgt || (d->src2 && !d->wgt2) || d->gout)) return -14;
-  if (rc == 1) {
-    if (!d->wgt || (d->src2 && !d->wgt2)) return -8;   // only halo tiles were supplied, but the halo path declined
-    if (d->gout) return -9;                            // the prologue side output exists only on the halo path
-    if (d->K <= 16)
-      rc = launch<16, 256, 1, 4, 64>(&dm, s);
-    else if (d->K <= 64)
-      rc = launch<64, 128, 2, 2, 64>(&dm, s);
-    else if (M <= tiny_m && d->splits > 1)    // tinier: 32-pixel tiles
-      rc = launch<128, 32, 2, 2, 64>(&dm, s);
-    else if (M <= small_m && d->splits > 1)   // tiny levels: 64-pixel tiles, half the split-K slabs
-      rc = launch<128, 64, 2, 2, 64>(&dm, s);
-    else
-      rc = launch<128, 128, 2, 2, 64>(&dm, s);
-  }
-  if (rc) return rc;
-  if (d->splits > 1 && combine && !tk) {
-    if (rows_ok) {
-      hipLaunchKernelGGL(splitk_reduce_rows, dim3(M / FMD_SPLIT_STATS_ROWS, (d->K + 63) / 64), dim3(256), 0, s, *d, M);
-    } else {
-      const size_t total = (size_t)M * d->K;
-      int blocks = (int)((total + 255) / 256);
-      if (blocks > 8192) blocks = 8192;
-      hipLaunchKernelGGL(splitk_reduce, dim3(blocks), dim3(256), 0, s, *d, M);
+  // a split conv's statistics: 16-pixel rows from the combine launch, or the ticketed epilogue's rows
+  const bool stats = (allow & FMD_CONV_WANT_STATS) &&
+                     (!split || (combine_rows_ok(d) && !d->out_f32 && !d->accumulate));
+  const bool offer_tk = split && combine, offer_fold = d->fold_st0 != nullptr;
+  const bool pro = d->pro_a || offer_fold;
+  p.combine_launch = split && combine;
+  p.stats_rows = !stats ? 0 : split ? FMD_SPLIT_STATS_ROWS : 64;
+  if (d->K > 16 && !d->force_generic) {
+    // 3x3 stride-1 problems with >= HALO_MIN_WG (32) workgroups of 16x16 tiles (x splits): the offers as made, then
+    // without the ticket, then without the fold (the caller folds with fmd_gn_prep and supplies pro_a / pro_b)
+    const bool tk_h = offer_tk && (allow & FMD_CONV_TICKET_HALO);
+    const bool forms[3][2] = {{tk_h, offer_fold}, {false, offer_fold}, {false, false}};
+    for (const auto& fm : forms) {
+      const ConvForm f = {fm[0], fm[1], pro, stats && (!split || fm[0])};
+      p.kernel = halo_decide(d, f, &D->H, &p.tile_rows);
+      if (!p.kernel) continue;
+      p.tickets = f.tk;
+      p.fold = f.fold;
+      if (f.tk) {   // the unsplit epilogue closes the conv: its 64-pixel rows
+        p.combine_launch = 0;
+        p.stats_rows = stats ? 64 : 0;
+      }
+      return 0;
     }
-    rc = (int)hipGetLastError();
   }
+  if (!d->wgt || (d->src2 && !d->wgt2)) return -8;   // only halo tiles were supplied, but the halo path declined
+  if (d->gout) return -9;                            // the prologue side output exists only on the halo path
+  // largest output (pixels) run on 64- / 32-pixel tiles when split-K
+  constexpr int small_m = 2048, tiny_m = 128;
+  D->ig = d->K <= 16 ? &IG_K16 : d->K <= 64 ? &IG_K64
+          : M <= tiny_m && split ? &IG_PX32    // tinier: 32-pixel tiles
+          : M <= small_m && split ? &IG_PX64   // tiny levels: 64-pixel tiles, half the split-K slabs
+          : &IG_PX128;
+  p.kernel = FMD_CONV_IGEMM;
+  p.bco = D->ig->bco;
+  p.bpx = D->ig->bpx;
+  ConvForm f = {offer_tk && (allow & FMD_CONV_TICKET_IGEMM), false, pro, stats};
+  if (f.tk && igemm_decide(*D->ig, d, f, &D->K) == 0) {
+    p.tickets = 1;
+    p.combine_launch = 0;
+    if (stats) p.stats_rows = D->K.stats_rows;
+    return 0;
+  }
+  f.tk = false;
+  f.stats = stats && !split;
+  if (igemm_decide(*D->ig, d, f, &D->K) == -11) {   // no statistics from this epilogue: the caller's own pass
+    f.stats = false;
+    p.stats_rows = 0;
+    igemm_decide(*D->ig, d, f, &D->K);
+  }
+  return 0;
+}
+
+// Launches exactly what conv_decide settled.
+int conv_go(const fmd_conv_desc* d, const Decision& D, fmd_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = D.p.kernel == FMD_CONV_IGEMM ? igemm_go(*D.ig, D.K, s)
+                                              : halo_go(D.H, D.p.kernel, D.p.tile_rows, stream);
+  return rc || !D.p.combine_launch ? rc : combine_go(d, s);
+}
+
+// The offers a descriptor's pointers make: the ticket (to either family) and the statistics.
+int offers(const fmd_conv_desc* d) {
+  return (d->tickets ? FMD_CONV_TICKET_HALO | FMD_CONV_TICKET_IGEMM : 0) | (d->stats ? FMD_CONV_WANT_STATS : 0);
+}
+
+// fmd_conv / fmd_conv_gn: decide, hold the descriptor to it -- every offer in d taken and d->stats written with the
+// rows the caller sized it for -- and go.  A caller that planned first (fmd_conv_plan) never sees these codes.
+int conv_run(const fmd_conv_desc* d, fmd_stream_t stream, bool combine) {
+  Decision D;
+  const int rc = conv_decide(d, offers(d), combine, &D);
+  if (rc) return rc;
+  if (d->stats && !D.p.stats_rows) return d->splits > 1 ? -5 : -11;
+  if (d->fold_st0 && !D.p.fold) return -13;
+  if (d->splits > 1 && d->tickets && combine &&
+      (!D.p.tickets || (d->stats && d->tickets_rows != D.p.stats_rows)))
+    return -14;
+  return conv_go(d, D, stream);
+}
+
+}  // namespace
+
+extern "C" int fmd_conv_plan(const fmd_conv_desc* d, int32_t allow, fmd_conv_plan_t* out) {
+  Decision D;
+  const int rc = conv_decide(d, allow | (d->stats ? FMD_CONV_WANT_STATS : 0), true, &D);
+  *out = D.p;
   return rc;
 }
 
@@ -1008,21 +1104,9 @@ extern "C" int fmd_conv_gn(const fmd_conv_desc* d, const fmd_gn_out_desc* g, fmd
 // epilogue (bias, bias2, per-sample bias, residual, data-gradient SiLU' / GN-backward sums, statistics).
 // Used by convolutions assembled from several partial launches (3-D convs as three depth-tap planes).
 extern "C" int fmd_conv_combine(const fmd_conv_desc* d, fmd_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
   if (!d->ws || d->splits < 1 || d->N < 1 || d->K < 1 || !d->out) return -1;
-  const int M = d->N * (d->Do > 0 ? d->Do : 1) * d->Ho * d->Wo;
-  const int HWo = (d->Do > 0 ? d->Do : 1) * d->Ho * d->Wo;
-  const bool rows_ok = d->K % 4 == 0 && M % FMD_SPLIT_STATS_ROWS == 0 && HWo % FMD_SPLIT_STATS_ROWS == 0;
-  if (d->stats && (!rows_ok || d->out_f32 || d->accumulate)) return -5;
-  if (rows_ok) {
-    hipLaunchKernelGGL(splitk_reduce_rows, dim3(M / FMD_SPLIT_STATS_ROWS, (d->K + 63) / 64), dim3(256), 0, s, *d, M);
-  } else {
-    const size_t total = (size_t)M * d->K;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(splitk_reduce, dim3(blocks), dim3(256), 0, s, *d, M);
-  }
-  return (int)hipGetLastError();
+  if (d->stats && (!combine_rows_ok(d) || d->out_f32 || d->accumulate)) return -5;
+  return combine_go(d, (hipStream_t)stream);
 }
 
 // 1x1 (or any generic-path) conv whose epilogue is the GroupNorm-backward apply of fmd_gn_bwd_apply:
@@ -1034,7 +1118,8 @@ extern "C" int fmd_conv_gn_apply(const fmd_conv_desc* d, const fmd_gn_apply_desc
   if (d->splits > 1 || d->stats || d->bias || d->bias2 || d->bias_nc || d->resid || d->ep_x0 || d->src2) return -5;
   if (!g || !g->dz || !g->x0 || !g->P || !g->Q || !g->R || !g->dx0 || (g->C0 % 8)) return -7;
   if (g->C0 < d->K && (!g->x1 || !g->dx1)) return -7;
-  // BK = 32: a 32 KiB LDS footprint keeps 4-5 of these memory-bound workgroups per CU in flight
-  if (d->K <= 64) return launch<64, 128, 2, 2, 32, true>(d, s, g);
-  return launch<128, 128, 2, 2, 32, true>(d, s, g);
+  const Igemm& I = d->K <= 64 ? IG_GNA64 : IG_GNA128;
+  KArgs A;
+  const int rc = igemm_decide(I, d, ConvForm{false, false, d->pro_a != nullptr, false}, &A, g);
+  return rc ? rc : igemm_go(I, A, s);
 }

@@ -739,8 +739,7 @@ __global__ void tile_weights_kernel(const bf16r* __restrict__ w, int K, int T, i
 
 }  // namespace
 
-// Called by fmd_conv when the problem qualifies (3x3, stride 1, pad 1, forward gather,
-// output tile 16x16 inside one image, >= 128 tiles).  Returns 1 if not applicable.
+// The halo dispatch (halo_args.h): 3x3, stride 1, pad 1, forward gather, 16x16 output tiles inside one image.
 // fewest workgroups (tiles x splits) the halo conv takes; smaller grids go to the implicit GEMM
 // (32: config D's latent sampler 81.7 / 81.4 -> 77.4 / 77.3 ms per 50 steps vs 128, interleaved A/B; the config B
 // train step unchanged within noise)
@@ -752,25 +751,29 @@ extern "C" int fmd_halo_set_min_workgroups(int32_t n) {
   return 0;
 }
 
-extern "C" int fmd_conv_halo(const fmd_conv_desc* d, fmd_stream_t stream) {
-  if (d->ks != 3 || d->stride != 1 || d->pad != 1 || d->transposed) return 1;
+int halo_decide(const fmd_conv_desc* d, const ConvForm& f, HArgs* Ap, int* rows) {
+  HArgs& A = *Ap;
+  *rows = 0;
+  if (d->ks != 3 || d->stride != 1 || d->pad != 1 || d->transposed) return 0;
   const bool d3 = d->Do > 0 || d->Ds > 0;
-  if (d3 && d->Do != (d->upsample ? 2 * d->Ds : d->Ds)) return 1;   // 3-D: stride-1 3x3x3 (nearest-x2)
+  if (d3 && d->Do != (d->upsample ? 2 * d->Ds : d->Ds)) return 0;   // 3-D: stride-1 3x3x3 (nearest-x2)
   const int Nn = d3 ? d->N * d->Do : d->N;                // images (3-D: depth slices)
-  if (d->splits > 1 && (!d->ws || (d->stats && !d->tickets))) return 1;   // ticketed splits: statistics in the epilogue
-  if (d->Ho % TH || d->Wo % TW) return 1;
-  if (d->upsample ? (d->Ho != 2 * d->Hs || d->Wo != 2 * d->Ws) : (d->Ho != d->Hs || d->Wo != d->Ws)) return 1;
-  if (!d->wgt_tiled || (d->src2 && !d->wgt2_tiled)) return 1;
-  if ((d->pro_a || d->fold_st0) && d->C0 + d->C1 > CMAX) return 1;   // the GN affine table holds CMAX channels
-  if (d->fold_st0 && (d3 || d->gout || d->pro_a || d->fold_G < 1 || (d->C0 + d->C1) % d->fold_G || d->fold_rows0 < 1 ||
-                      (d->Hs * d->Ws) % d->fold_rows0 ||
-                      (d->C1 && (!d->fold_st1 || d->fold_rows1 < 1 || (d->Hs * d->Ws) % d->fold_rows1))))
-    return 1;   // the in-kernel fold: 2-D, whole slab rows, one source of statistics per input
-  if (d->gout && (d->C0 + d->C1) % BK) return 1;     // G side output: whole 32-channel chunks
+  if (d->splits > 1 && (!d->ws || (f.stats && !f.tk))) return 0;   // ticketed splits: statistics in the epilogue
+  if (d->Ho % TH || d->Wo % TW) return 0;
+  if (d->upsample ? (d->Ho != 2 * d->Hs || d->Wo != 2 * d->Ws) : (d->Ho != d->Hs || d->Wo != d->Ws)) return 0;
+  if (!d->wgt_tiled || (d->src2 && !d->wgt2_tiled)) return 0;
+  if (f.pro && d->C0 + d->C1 > CMAX) return 0;   // the GN affine table holds CMAX channels
+  if (f.fold && (d3 || d->gout || d->pro_a || d->fold_G < 1 || (d->C0 + d->C1) % d->fold_G || d->fold_rows0 < 1 ||
+                 (d->Hs * d->Ws) % d->fold_rows0 ||
+                 (d->C1 && (!d->fold_st1 || d->fold_rows1 < 1 || (d->Hs * d->Ws) % d->fold_rows1))))
+    return 0;   // the in-kernel fold: 2-D, whole slab rows, one source of statistics per input
+  if (d->gout && (d->C0 + d->C1) % BK) return 0;     // G side output: whole 32-channel chunks
   if ((long long)Nn * d->Hs * d->Ws * (d->C0 > d->C1 ? d->C0 : d->C1) >= (1LL << 31) ||
-      (long long)Nn * d->Ho * d->Wo * (d->C2 > d->C3 ? d->C2 : d->C3) >= (1LL << 31)) return 1;   // 32-bit offsets
-  HArgs A;
+      (long long)Nn * d->Ho * d->Wo * (d->C2 > d->C3 ? d->C2 : d->C3) >= (1LL << 31)) return 0;   // 32-bit offsets
   A.d = *d;
+  if (!f.tk) A.d.tickets = nullptr;
+  if (!f.fold) A.d.fold_st0 = nullptr;
+  if (!f.stats) A.d.stats = nullptr;
   A.C = d->C0 + d->C1;
   A.C23 = d->src2 ? d->C2 + d->C3 : 0;
   A.tiles_x = d->Wo / TW;
@@ -785,23 +788,28 @@ extern "C" int fmd_conv_halo(const fmd_conv_desc* d, fmd_stream_t stream) {
   A.nsteps_slots = A.nchunk1 * 9 + A.nchunk2;
   A.splits = d->splits > 1 ? d->splits : 1;
   A.cps = (A.nchunk1 + A.splits - 1) / A.splits;
-  if (A.splits > 1 && (A.splits - 1) * A.cps >= A.nchunk1) return 1;   // every split owns >= 1 chunk
+  if (A.splits > 1 && (A.splits - 1) * A.cps >= A.nchunk1) return 0;   // every split owns >= 1 chunk
   A.wt = (const bf16r*)d->wgt_tiled;
   A.wt2 = (const bf16r*)d->wgt2_tiled;
-  A.fold_E0 = d->fold_st0 ? d->Hs * d->Ws / d->fold_rows0 : 0;
-  A.fold_E1 = d->fold_st0 && d->C1 ? d->Hs * d->Ws / d->fold_rows1 : 0;
-  A.fold_inv = d->fold_st0 ? 1.0 / ((double)(A.C / d->fold_G) * d->Hs * d->Ws) : 0.0;
+  A.fold_E0 = f.fold ? d->Hs * d->Ws / d->fold_rows0 : 0;
+  A.fold_E1 = f.fold && d->C1 ? d->Hs * d->Ws / d->fold_rows1 : 0;
+  A.fold_inv = f.fold ? 1.0 / ((double)(A.C / d->fold_G) * d->Hs * d->Ws) : 0.0;
   A.dbg = g_dbg;
   A.tbuf = g_tbuf;
   const int nwg = Nn * A.tiles_x * A.tiles_y * A.ntc;
-  if (nwg * A.splits < g_halo_min_wg) return 1;   // too few workgroups to fill the chip: the implicit GEMM wins
-  const int pro = d->pro_a || d->fold_st0 ? (d->pro_silu ? 2 : 1) : 0;
-  {   // the v9b kernel (csrc/conv_halo9.hip) takes every problem it supports
-    const int rc9 = halo9_launch(A, pro, stream);
-    if (rc9 != 1 || d->fold_st0 || (d->tickets && A.splits > 1)) return rc9;   // the fold and the in-launch combine exist only in v9b
-  }
+  if (nwg * A.splits < g_halo_min_wg) return 0;   // too few workgroups to fill the chip: the implicit GEMM wins
+  *rows = halo9_decide(A, f.tk);   // the v9b kernel (csrc/conv_halo9.hip) takes every problem it supports
+  if (*rows) return FMD_CONV_HALO9;
+  if (f.fold || f.tk) return 0;   // the fold and the in-launch combine exist only in v9b
+  return FMD_CONV_HALO8;
+}
+
+int halo_go(const HArgs& A, int kernel, int rows, fmd_stream_t stream) {
+  if (kernel == FMD_CONV_HALO9) return halo9_go(A, rows, stream);
+  const fmd_conv_desc* d = &A.d;
+  const int pro = d->pro_a ? (d->pro_silu ? 2 : 1) : 0;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 g(nwg, A.splits);
+  const dim3 g(d->N * A.tiles_x * A.tiles_y * A.ntc, A.splits);
   const dim3 blk(NT);
   if (d->gout) {   // prologue side output (fmd_conv checked pro_a)
     if (d->upsample) {
@@ -823,6 +831,15 @@ extern "C" int fmd_conv_halo(const fmd_conv_desc* d, fmd_stream_t stream) {
     else hipLaunchKernelGGL((conv3x3_halo<false, 0>), g, blk, 0, st, A);
   }
   return (int)hipGetLastError();
+}
+
+extern "C" int fmd_conv_halo(const fmd_conv_desc* d, fmd_stream_t stream) {
+  const ConvForm f = {d->splits > 1 && d->tickets, d->fold_st0 != nullptr, d->pro_a || d->fold_st0, d->stats != nullptr};
+  if (f.tk && f.stats && d->tickets_rows != 64) return 1;   // the ticketed epilogue writes 64-pixel rows
+  HArgs A;
+  int rows;
+  const int kernel = halo_decide(d, f, &A, &rows);
+  return kernel ? halo_go(A, kernel, rows, stream) : 1;
 }
 
 // Debug hook (not part of the public ABI): ablation flags of the next launches (see HArgs::dbg).

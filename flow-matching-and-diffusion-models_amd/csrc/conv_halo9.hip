@@ -793,7 +793,8 @@ int g_th8_max_wg = 1024;
 int g_th4_max_wg = 512;
 
 template <int THT>
-int halo9_go(const HArgs& A, int pro, fmd_stream_t stream) {
+int halo9_launch(const HArgs& A, fmd_stream_t stream) {
+  const int pro = A.d.pro_a || A.d.fold_st0 ? (A.d.pro_silu ? 2 : 1) : 0;
   const int nwg = A.d.N * A.tiles_x * A.tiles_y * A.ntc;
   const dim3 g(nwg, A.splits);
   const dim3 blk(NT9);
@@ -816,28 +817,26 @@ extern "C" int fmd_halo_set_th8_max_workgroups(int32_t n) {
   return 0;
 }
 
-int halo9_launch(const HArgs& A, int pro, fmd_stream_t stream) {
+int halo9_decide(const HArgs& A, bool tk) {
   const fmd_conv_desc* d = &A.d;
-  if (d->gout) return 1;
-  if (d->upsample && d->src2) return 1;
-  const bool tk = A.splits > 1 && d->tickets;   // split-K with the in-launch combine and the unsplit epilogue
-  if ((A.splits <= 1 || tk) && (d->K % BCO || d->out_f32 || d->accumulate || (d->resid && d->ep_x0))) return 1;
-  if (A.splits > 1 && (d->out_f32 || d->accumulate)) return 1;
-  if (tk && (A.depth || d->n_tickets < (long long)A.d.N * A.tiles_x * (d->Ho / 4) * A.ntc ||
-             (d->stats && d->tickets_rows != 64)))
-    return 1;
+  if (d->gout) return 0;
+  if (d->upsample && d->src2) return 0;
+  // tk: split-K with the in-launch combine and the unsplit epilogue
+  if ((A.splits <= 1 || tk) && (d->K % BCO || d->out_f32 || d->accumulate || (d->resid && d->ep_x0))) return 0;
+  if (A.splits > 1 && (d->out_f32 || d->accumulate)) return 0;
+  if (tk && (A.depth || d->n_tickets < (long long)A.d.N * A.tiles_x * (d->Ho / 4) * A.ntc)) return 0;
   const long long nwg16 = (long long)A.d.N * A.tiles_x * A.tiles_y * A.ntc * A.splits;
-  if (tk && !(nwg16 < g_th8_max_wg && d->Ho % 8 == 0)) return 1;   // the combine exists in the 8- and 4-row instances
-  if (nwg16 < g_th8_max_wg && d->Ho % 8 == 0) {
-    HArgs A8 = A;
-    A8.tiles_y = d->Ho / 8;
-    if (2 * nwg16 < g_th4_max_wg && !A.depth) {   // 4-row tiles: twice the 8-row grid, still under one round
-      A8.tiles_y = d->Ho / 4;
-      return halo9_go<4>(A8, pro, stream);
-    }
-    return halo9_go<8>(A8, pro, stream);
-  }
-  return halo9_go<TH>(A, pro, stream);
+  const bool th8 = nwg16 < g_th8_max_wg && d->Ho % 8 == 0;
+  if (tk && !th8) return 0;   // the combine exists in the 8- and 4-row instances
+  if (!th8) return TH;
+  return 2 * nwg16 < g_th4_max_wg && !A.depth ? 4 : 8;   // 4-row tiles: twice the 8-row grid, still under one round
+}
+
+int halo9_go(const HArgs& A, int rows, fmd_stream_t stream) {
+  if (rows == TH) return halo9_launch<TH>(A, stream);
+  HArgs A8 = A;
+  A8.tiles_y = A.d.Ho / rows;
+  return rows == 4 ? halo9_launch<4>(A8, stream) : halo9_launch<8>(A8, stream);
 }
 
 extern "C" int fmd_halo_set_th4_max_workgroups(int32_t n) {
@@ -982,7 +981,7 @@ extern "C" int fmd_conv_s2d(const fmd_conv_desc* d, fmd_stream_t stream) {
   if (nwg < 128) return 1;
   const int pro = d->pro_a ? (d->pro_silu ? 2 : 1) : 0;
   hipStream_t st = (hipStream_t)stream;
-  if (nwg < g_th8_max_wg) {   // 8-row tiles on a one-round grid (as halo9_launch)
+  if (nwg < g_th8_max_wg) {   // 8-row tiles on a one-round grid (as halo9_decide)
     A.tiles_y = d->Ho / 8;
     const dim3 g(2 * nwg), blk(NT9);
     if (pro == 2) hipLaunchKernelGGL((conv3x3_halo9b<false, 2, 1, 8>), g, blk, 0, st, A);
@@ -1035,7 +1034,7 @@ extern "C" int fmd_conv_d2s(const fmd_conv_desc* d, fmd_stream_t stream) {
   A.dbg = 0;
   const int nwg = A.d.N * A.tiles_x * A.tiles_y * A.ntc;
   if (nwg < 128) return 1;
-  if (nwg < g_th8_max_wg) {   // 8-row tiles on a one-round grid (as halo9_launch)
+  if (nwg < g_th8_max_wg) {   // 8-row tiles on a one-round grid (as halo9_decide)
     A.tiles_y = d->Hs / 8;
     hipLaunchKernelGGL((conv3x3_halo9b<false, 0, 2, 8>), dim3(2 * nwg), dim3(NT9), 0, (hipStream_t)stream, A);
     return (int)hipGetLastError();

@@ -25,6 +25,23 @@ struct HArgs {
                                // 16 no SiLU' in the epilogue, 32 no statistics, 64 no side-tile loads
 };
 
-// v9 kernel (csrc/conv_halo9.hip): launches the problem A describes if it qualifies; returns 1 (not applicable),
-// 0 (launched) or a hipError_t.  pro: 0 raw input, 1 GroupNorm affine, 2 affine + SiLU.
-int halo9_launch(const HArgs& A, int pro, fmd_stream_t stream);
+// One form of a conv problem as the dispatch weighs it (fmd_conv_plan): the caller's offers taken or dropped,
+// whatever the descriptor's pointers say.
+struct ConvForm {
+  bool tk;      // split-K (splits > 1) combined inside the launch (d->tickets taken)
+  bool fold;    // GroupNorm fold in the prologue (d->fold_* taken)
+  bool pro;     // a GroupNorm prologue of either kind (a dropped fold comes back as pro_a / pro_b)
+  bool stats;   // statistics from this launch's epilogue
+};
+
+// The halo decision, host arithmetic only (csrc/conv_halo.hip): the kernel that takes d in form f -- FMD_CONV_HALO9
+// (*rows = 16 / 8 / 4 tile rows), FMD_CONV_HALO8, or 0 when the problem goes to the implicit GEMM -- and its launch
+// arguments in *A.  halo_go launches exactly that; returns 0 or a hipError_t.
+int halo_decide(const fmd_conv_desc* d, const ConvForm& f, HArgs* A, int* rows);
+int halo_go(const HArgs& A, int kernel, int rows, fmd_stream_t stream);
+
+// v9b kernel (csrc/conv_halo9.hip): the tile rows (16 / 8 / 4) of the instance that takes A, 0 when none does; and its
+// launch.  tk: the split is combined inside the launch.  The prologue kind comes from A.d (raw input, GroupNorm
+// affine, affine + SiLU).
+int halo9_decide(const HArgs& A, bool tk);
+int halo9_go(const HArgs& A, int rows, fmd_stream_t stream);

@@ -35,6 +35,16 @@ class ConvDesc(C.Structure):
     ]
 
 
+class ConvPlan(C.Structure):
+    """Mirror of ``fmd_conv_plan_t``."""
+    _fields_ = [("kernel", i32), ("tile_rows", i32), ("bco", i32), ("bpx", i32), ("tickets", i32),
+                ("combine_launch", i32), ("stats_rows", i32), ("fold", i32)]
+
+
+CONV_IGEMM, CONV_HALO8, CONV_HALO9 = 1, 2, 3                      # fmd_conv_plan_t.kernel (FMD_CONV_*)
+CONV_TICKET_HALO, CONV_TICKET_IGEMM, CONV_WANT_STATS = 1, 2, 4    # fmd_conv_plan's allow bits
+
+
 class WgradDesc(C.Structure):
     """Mirror of ``fmd_wgrad_desc``."""
     _fields_ = [
@@ -99,6 +109,7 @@ GB_MAX = 64   # FMD_GB_MAX
 # name -> argtypes (restype is int32 unless listed in _RESTYPE)
 SIGNATURES = {
     "fmd_conv": [C.POINTER(ConvDesc), p],
+    "fmd_conv_plan": [C.POINTER(ConvDesc), i32, C.POINTER(ConvPlan)],
     "fmd_conv_halo": [C.POINTER(ConvDesc), p],
     "fmd_conv_gn_apply": [C.POINTER(ConvDesc), C.POINTER(GnApplyDesc), p],
     "fmd_conv_gn": [C.POINTER(ConvDesc), C.POINTER(GnOutDesc), p],

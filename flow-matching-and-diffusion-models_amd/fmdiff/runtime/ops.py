@@ -246,6 +246,17 @@ BPX64_M = 2048
 BPX32_M = 128
 
 
+def igemm_split_tile(K, M):
+    """(bco, bpx): output channels x pixels of the implicit-GEMM tile a problem runs on IF it runs split-K (the 64- /
+    32-pixel tiles exist only for splits > 1) -- what :func:`_choose_splits` counts workgroups with, before the
+    split count the plan needs is known.  tests/test_conv_plan.py holds it to fmd_conv_plan's answer."""
+    if K <= 16:
+        return 16, 256
+    if K <= 64:
+        return 64, 128
+    return 128, (128 if M > BPX64_M else 32 if M <= BPX32_M else 64)
+
+
 def _choose_splits(M, K, nk, bpx=128, bco=128):
     tiles = -(-M // bpx) * -(-K // bco)
     if tiles >= NUM_CU or nk < 8:
@@ -415,11 +426,6 @@ def conv(src0, K, wgt, *, src1=None, ks=3, stride=1, pad=1, upsample=False, tran
         if tw is not None and tw.numel() < -(-K // 128) * 128 * -(-cc // HALO_BK) * HALO_BK * taps:
             raise ValueError(f"halo-tiled weights ({tw.numel()} elements) too small for K={K}, C={cc}")
     nk = -(-(C0 + C1) // 64) * T + (-(-(d.C2 + d.C3) // 64) if src2 is not None else 0)
-    bco = 16 if K <= 16 else (64 if K <= 64 else 128)
-    # pixel tile the generic kernel will use IF it runs split-K (csrc/conv.hip fmd_conv: the 64 / 32-pixel tiles
-    # exist only for splits > 1); re-decided below once the split count is known
-    bpx_split = 256 if K <= 16 else (128 if K <= 64 or M > BPX64_M else (32 if M <= BPX32_M else 64))
-    bpx = bpx_split
     if d3:   # depth-tap chunks on the halo kernel: pre-tiled (kz, channel block) weights are required
         halo = (not force_generic and wgt_tiled is not None and Do == (2 * Ds if upsample else Ds) and
                 halo_eligible(N * Do, Hs, Ho, Wo, K, ks, stride, pad, upsample, transposed, C0 + C1,
@@ -462,37 +468,35 @@ def conv(src0, K, wgt, *, src1=None, ks=3, stride=1, pad=1, upsample=False, tran
         d.gout = _p(gout)
     if halo:
         splits = halo_splits(N * max(Do, 1), Ho, Wo, K, C0 + C1, 3 if d3 else 1)
-        bpx = 256
         if wgt_tiled is None:
             wgt_tiled = tile_weights(wgt)
         if src2 is not None and wgt2_tiled is None:
             wgt2_tiled = tile_weights(wgt2)
         d.wgt_tiled, d.wgt2_tiled = _p(wgt_tiled), _p(wgt2_tiled)
     if splits is None:
+        bco, bpx = igemm_split_tile(K, M)
         splits = _choose_splits(M, K, nk, bpx, bco)
-    if not halo and splits <= 1 and K > 64:
-        bpx = 128   # the kernel's rule: small-pixel tiles only with split-K
     ws = None
     if splits > 1:
         ws = torch.empty((splits, M, K), device=dev, dtype=F32)
         d.ws, d.splits = _p(ws), splits
     else:
         d.splits = 1
-    ticket, trows = split_ticket(halo, splits, K, M, bpx, bco, d3=d3, transposed=transposed, stride=stride, ks=ks,
-                                 pad=pad, Ho=Ho, Wo=Wo, out_f32=out_f32, accumulate=accumulate,
-                                 resid_and_ep=resid is not None and ep is not None, gout=gout is not None)
-    st = None
-    # statistics from the conv epilogue (no split, or the in-launch combine) or from the split-K combine launch
-    # (csrc/conv.hip splitk_reduce_rows)
-    fused_stats = want_stats and (max(Do, 1) * Ho * Wo) % 64 == 0 and (
-        (splits == 1 and M % bpx == 0) or (splits > 1 and K % 4 == 0 and not out_f32 and not accumulate))
-    if fused_stats:
-        rows = 64 if splits == 1 else trows if ticket else SPLIT_STATS_ROWS
-        slab = torch.empty((M // rows, K, 2), device=dev, dtype=F32)
-        d.stats = _p(slab)
-        st = Stats(slab, rows)
-    if (gn is not None and CONV_GN and splits > 1 and not want_stats and d.stats is None and not out_f32
-            and not accumulate and ep is None and conv_gn_eligible(K, gn["groups"], N)):
+    with_gn = (gn is not None and CONV_GN and splits > 1 and not want_stats and not out_f32 and not accumulate
+               and ep is None and conv_gn_eligible(K, gn["groups"], N))
+    # the offers (the fold is in d): statistics from the launch where the images are whole 64-pixel rows, and the
+    # split combined inside the launch; the plan says which of them the kernel that runs takes
+    allow = _lib.CONV_WANT_STATS if want_stats and (max(Do, 1) * Ho * Wo) % 64 == 0 else 0
+    if splits > 1 and not with_gn:
+        allow |= (_lib.CONV_TICKET_HALO if HALO_TICKET else 0) | (_lib.CONV_TICKET_IGEMM if SPLIT_TICKET else 0)
+        d.n_tickets = SMALL_TICKETS
+    L, plan = _lib.lib(), _lib.ConvPlan()
+    _lib.check(L.fmd_conv_plan(C.byref(d), allow, C.byref(plan)), "fmd_conv_plan")
+    if fold is not None and not plan.fold:   # the fold as its own launch
+        pro = _fold_now(fold, N, Hs * Ws, C0, C1)
+        _clear_fold(d)
+        d.pro_a, d.pro_b, d.pro_silu = _p(pro[0]), _p(pro[1]), int(pro[2])
+    if with_gn:
         a = torch.empty((N, K), device=dev, dtype=F32)
         b = torch.empty((N, K), device=dev, dtype=F32)
         mr = torch.empty((N, gn["groups"], 2), device=dev, dtype=F32)
@@ -505,46 +509,20 @@ def conv(src0, K, wgt, *, src1=None, ks=3, stride=1, pad=1, upsample=False, tran
         _lib.call("fmd_conv_gn", C.byref(d), C.byref(g), stream())
         gn["res"] = (a, b, mr, t)
         return out, None
-    if ticket:
-        d.tickets, d.n_tickets, d.tickets_rows = _p(_small_workspace(dev)[1]), SMALL_TICKETS, trows
-    rc = int(_lib.lib().fmd_conv(C.byref(d), stream()))
-    if rc == -14:   # the halo kernel did not take the in-launch combine: the combine launch (16-pixel statistics rows)
-        d.tickets, d.n_tickets, d.tickets_rows = None, 0, 0
-        if st is not None:
-            slab = torch.empty((M // SPLIT_STATS_ROWS, K, 2), device=dev, dtype=F32)
-            d.stats = _p(slab)
-            st = Stats(slab, SPLIT_STATS_ROWS)
-        rc = int(_lib.lib().fmd_conv(C.byref(d), stream()))
-    if rc == -13 and fold is not None:   # the halo kernel did not take it: the fold as its own launch
-        pro = _fold_now(fold, N, Hs * Ws, C0, C1)
-        _clear_fold(d)
-        d.pro_a, d.pro_b, d.pro_silu = _p(pro[0]), _p(pro[1]), int(pro[2])
-        rc = int(_lib.lib().fmd_conv(C.byref(d), stream()))
-    _lib.check(rc, "fmd_conv")
-    if want_stats == "free":   # only statistics the kernel emits for free; the consumer derives others lazily
-        return out, st
-    if want_stats and not fused_stats:
+    st = None
+    if plan.stats_rows:
+        slab = torch.empty((M // plan.stats_rows, K, 2), device=dev, dtype=F32)
+        d.stats = _p(slab)
+        st = Stats(slab, plan.stats_rows)
+    if plan.tickets:
+        d.tickets, d.tickets_rows = _p(_small_workspace(dev)[1]), plan.stats_rows
+    _lib.check(L.fmd_conv(C.byref(d), stream()), "fmd_conv")
+    if want_stats is True and st is None:   # "free": only statistics the kernel emits; the consumer derives others
         if ep is not None:
             st = channel_stats(out, y=(ep[0], ep[1], ep[0].shape[-1]))
         else:
             st = channel_stats(out)
     return out, st
-
-
-def split_ticket(halo, splits, K, M, bpx, bco, *, d3=False, transposed=False, stride=1, ks=3, pad=1, Ho=0, Wo=0,
-                 out_f32=False, accumulate=False, resid_and_ep=False, gout=False):
-    """(ticket, rows): whether a split-K conv combines its parts inside the launch (fmd_conv_desc.tickets), and the
-    pixels per statistics row its epilogue then writes -- mirroring the kernels' conditions.  The halo kernel
-    (csrc/conv_halo9.hip halo9_launch): 2-D, whole 128-cout tiles, the unsplit epilogue's forms, no G side output,
-    rows of 64 pixels.  The implicit GEMM (csrc/conv.hip launch): 2-D, whole pixel and cout tiles, no parity classes
-    (transposed stride-2 3x3), one row per wave's pixels (bpx / 2; 64 for K <= 16, whose tile has 4 waves across)."""
-    if splits <= 1 or d3 or out_f32 or accumulate:
-        return False, 0
-    if halo:
-        return bool(HALO_TICKET and K % 128 == 0 and not resid_and_ep and not gout), 64
-    par = transposed and stride == 2 and ks == 3 and pad == 1 and Ho % 2 == 0 and Wo % 2 == 0
-    ok = SPLIT_TICKET and not par and M % bpx == 0 and K % bco == 0
-    return bool(ok), (64 if K <= 16 else bpx // 2)
 
 
 def _set_fold(d, f):

@@ -84,8 +84,9 @@ typedef struct fmd_conv_desc {
                                in place of pro_a / pro_b: each workgroup computes its sample's affine from the
                                producers' statistics slab of src0 [N*Hs*Ws/fold_rows0][C0][2] (and of src1), the
                                groups, eps, gamma, beta and the scale-shift rows -- gn_prep's fold, without its
-                               launch.  fmd_conv returns -13 when the v9b halo kernel does not take the problem
-                               (the caller folds with fmd_gn_prep instead).  NULL = off */
+                               launch.  An offer: fmd_conv_plan says whether the kernel that runs takes it
+                               (plan.fold); where it does not the caller folds with fmd_gn_prep and passes pro_a /
+                               pro_b instead (an unplanned fmd_conv returns -13).  NULL = off */
   int32_t fold_rows0;
   const float* fold_st1;
   int32_t fold_rows1;
@@ -99,15 +100,44 @@ typedef struct fmd_conv_desc {
                                implicit GEMM on whole tiles): [n_tickets] arrival counters, zero on entry and left
                                zero; d->ws holds the parts' fp32 tiles (same [splits][M][K] size) and the statistics
                                come from the conv epilogue, one row per tickets_rows pixels (64 on the halo kernel,
-                               the wave's pixel range on the implicit GEMM).  fmd_conv returns -14 when the kernel
-                               that takes the problem cannot combine it so or would write other rows (the caller then
-                               runs the two-launch split).  NULL = the separate combine launch */
+                               the wave's pixel range on the implicit GEMM).  An offer: fmd_conv_plan says whether
+                               the kernel that runs takes it (plan.tickets) and the rows it writes (plan.stats_rows);
+                               where it does not the caller clears it (an unplanned fmd_conv returns -14 when the
+                               ticket is not taken or tickets_rows is not the rows written).  NULL = the separate
+                               combine launch */
   int32_t n_tickets;
   int32_t tickets_rows;     /* pixels per statistics row the caller allocated for a ticketed conv with stats */
 } fmd_conv_desc;
 
-/* Dispatches 3x3 stride-1 forward-gather problems with >= 128 16x16 output tiles to the
- * halo-tiled kernel (csrc/conv_halo.hip), everything else to the implicit GEMM (csrc/conv.hip). */
+/* What fmd_conv will launch for a descriptor: a host-side query, nothing is launched.  fmd_conv runs the same
+ * decision, so the plan and the launch agree. */
+#define FMD_CONV_IGEMM 1          /* plan.kernel: implicit GEMM (csrc/conv.hip), tile bco x bpx */
+#define FMD_CONV_HALO8 2          /* halo-tiled 3x3, round-3 kernel (csrc/conv_halo.hip) */
+#define FMD_CONV_HALO9 3          /* halo-tiled 3x3, v9b (csrc/conv_halo9.hip), tile_rows x 16 pixel tiles */
+#define FMD_CONV_TICKET_HALO 1    /* allow: the in-launch combine is offered to the halo kernel */
+#define FMD_CONV_TICKET_IGEMM 2   /* allow: ... to the implicit GEMM */
+#define FMD_CONV_WANT_STATS 4     /* allow: statistics are wanted (d->stats set counts too) */
+typedef struct fmd_conv_plan_t {
+  int32_t kernel;           /* FMD_CONV_IGEMM / FMD_CONV_HALO8 / FMD_CONV_HALO9 */
+  int32_t tile_rows;        /* halo v9b: 16, 8 or 4 output rows per tile; else 0 */
+  int32_t bco, bpx;         /* implicit GEMM: output channels x pixels per tile; else 0 */
+  int32_t tickets;          /* 1: d->tickets is taken, the split is combined inside the launch */
+  int32_t combine_launch;   /* 1: a splitk_reduce* launch follows the conv launch */
+  int32_t stats_rows;       /* pixels per row the launch writes into d->stats; 0: no kernel emits them for this
+                               problem (the caller leaves d->stats NULL and runs fmd_channel_stats) */
+  int32_t fold;             /* 1: d->fold_* is consumed in the prologue; 0: the caller must supply pro_a / pro_b */
+} fmd_conv_plan_t;
+/* Plans d with the caller's offers: the in-launch combine of a split (allow: to which kernel families; d->n_tickets
+ * counters; d->tickets itself may still be NULL), the statistics (allow) and the fold (d->fold_*).  A declined offer is
+ * dropped, the ticket before the fold, until the plan is a form that runs.  The caller then sets d->tickets and
+ * tickets_rows = stats_rows if plan.tickets (else leaves them NULL / 0), replaces fold_* by pro_a / pro_b unless
+ * plan.fold, sets d->stats to a slab of stats_rows-pixel rows (or leaves it NULL), and calls fmd_conv once.  Returns
+ * 0, or the negative code of a descriptor no kernel runs. */
+int fmd_conv_plan(const fmd_conv_desc* d, int32_t allow, fmd_conv_plan_t* out);
+/* Dispatches 3x3 stride-1 forward-gather problems with enough 16x16 output tiles to the halo-tiled kernels
+ * (csrc/conv_halo.hip, csrc/conv_halo9.hip), everything else to the implicit GEMM (csrc/conv.hip): fmd_conv_plan's
+ * decision with both families allowed the ticket, then the launch.  Every offer in d must be taken as made: -13 (fold
+ * declined), -14 (ticket declined, or tickets_rows is not the rows written), -5 / -11 (d->stats cannot be written). */
 int fmd_conv(const fmd_conv_desc* d, fmd_stream_t s);
 /* Halo-tiled 3x3 stride-1 conv; returns 1 (nothing launched) when the problem does not qualify. */
 int fmd_conv_halo(const fmd_conv_desc* d, fmd_stream_t s);

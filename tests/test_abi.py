@@ -45,7 +45,8 @@ def test_library_exports_every_declared_symbol():
 def test_struct_mirrors_match_header_field_order():
     from fmdiff import _lib
     src = open(HEADER).read()
-    for cname, py in (("fmd_conv_desc", _lib.ConvDesc), ("fmd_wgrad_desc", _lib.WgradDesc),
+    for cname, py in (("fmd_conv_desc", _lib.ConvDesc), ("fmd_conv_plan_t", _lib.ConvPlan),
+                      ("fmd_wgrad_desc", _lib.WgradDesc),
                       ("fmd_gn_apply_desc", _lib.GnApplyDesc), ("fmd_gb_job", _lib.GbJob),
                       ("fmd_conv_small_desc", _lib.ConvSmallDesc),
                       ("fmd_lincomb_desc", _lib.LincombDesc)):

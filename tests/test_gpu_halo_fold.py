@@ -25,8 +25,8 @@ CASES = {
 }
 
 
-def _inputs(name):
-    N, H, C0, C1, K, rows, ss = CASES[name]
+def _inputs(name, case=None):
+    N, H, C0, C1, K, rows, ss = case or CASES[name]
     g = torch.Generator().manual_seed(sum(map(ord, name)))
     x0 = (torch.randn(N, H, H, C0, generator=g) * 1.2 + 0.3).to(torch.bfloat16).to(DEV)
     x1 = (torch.randn(N, H, H, C1, generator=g) * 0.8 - 0.2).to(torch.bfloat16).to(DEV) if C1 else None
@@ -98,3 +98,39 @@ def test_halo_fold_falls_back_where_the_halo_path_declines(monkeypatch):
         ref, _ = ops.conv(x0, K, wk, pro=(a, b, True), **kw)
         torch.cuda.synchronize()
         assert torch.equal(got, ref), kw
+
+
+def test_halo_fold_with_a_declined_ticket_runs_the_two_launch_split(monkeypatch):
+    """16-row tiles only (HALO_TH8_MAX_WG = 0: no in-launch combine) on the smallest halo-eligible split problem,
+    8 tiles x 4 splits, with the fold and a ticket offered: the plan drops the ticket and keeps the fold -- the
+    two-launch split with the combine's 16-pixel statistics rows.
+    Against gn_prep -> pro=(a, b) on the same split: the folds differ only in summation order, a bf16 step at most."""
+    from fmdiff import _lib
+    from fmdiff.runtime import ops, tuning
+    monkeypatch.setattr(ops, "HALO_FOLD", True)
+    monkeypatch.setattr(ops, "HALO_TICKET", True)
+    N, H, C, K = 8, 16, 256, 128
+    x0, _, w, gamma, beta, emb, rows = _inputs("split16_th8_off", (N, H, C, 0, K, 64, False))
+    assert ops.halo_splits(N, H, H, K, C) == 4 and ops.halo_eligible(N, H, H, H, K, Cin=C, pro=True)
+    wk = ops.prep_weights(w, 0)
+    f = _fold_dict(ops, x0, None, gamma, beta, emb, rows)
+    a, b, _ = ops.gn_prep(f["st0"], None, N, H * H, C, 0, 32, 1e-6, gamma, beta)
+    L = _lib.lib()
+    try:
+        assert L.fmd_halo_set_th8_max_workgroups(0) == 0
+        got, st = ops.conv(x0, K, wk, pro_fold=f, want_stats=True)
+        ref, _ = ops.conv(x0, K, wk, pro=(a, b, True), want_stats=True)
+        torch.cuda.synchronize()
+    finally:
+        L.fmd_halo_set_th8_max_workgroups(tuning.get("HALO_TH8_MAX_WG"))
+    assert st.rows == ops.SPLIT_STATS_ROWS
+    err, scale = (got.float() - ref.float()).abs().max().item(), ref.float().abs().max().item()
+    print(f"[halo fold, ticket declined] vs gn_prep path {err / scale:.2e}")
+    assert err <= 8e-3 * scale, (err, scale)
+    # statistics: per sample, the fp64 sums of the kernel's own bf16 outputs
+    y = got.double().reshape(N, -1, K)
+    tot = st.slab.double().reshape(N, -1, K, 2).sum(1)
+    for c, t in ((0, y), (1, y * y)):
+        assert ((tot[..., c] - t.sum(1)).abs() <= 1e-5 * t.abs().sum(1) + 1e-6).all(), c
+    # no ticket was taken: the workspace stays zero
+    assert int(ops._small_workspace(got.device)[1].abs().sum()) == 0
