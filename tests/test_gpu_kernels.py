@@ -512,7 +512,8 @@ def test_attention(raw, T, heads, dh):
     O = ops()
     B = 2
     inner = heads * dh
-    qkv = (torch.randn(B, T, 3 * inner) * 0.5).to(torch.bfloat16)
+    g = torch.Generator().manual_seed(1000 * T + 10 * dh + raw)
+    qkv = (torch.randn(B, T, 3 * inner, generator=g) * 0.5).to(torch.bfloat16)
     f = qkv.float().requires_grad_()
     if raw:
         flat = f.transpose(1, 2).reshape(B, heads, T, 3 * dh)   # (B, 3*inner, T) read raw
@@ -524,7 +525,7 @@ def test_attention(raw, T, heads, dh):
         o_tok = o.reshape(B, inner, T).transpose(1, 2)          # raw reinterpretation as (inner, T)
     else:
         o_tok = o.transpose(1, 2).reshape(B, T, inner)
-    do = torch.randn_like(o_tok).to(torch.bfloat16).float()
+    do = torch.randn(o_tok.shape, generator=g).to(torch.bfloat16).float()
     o_tok.backward(do)
     og, lse = O.attention_fwd(qkv.to(DEV), T, heads, dh, raw)
     _close(og, o_tok.detach())
@@ -543,7 +544,8 @@ def test_linear_attention(raw, T, heads, dh):
     O = ops()
     B = 2
     inner = heads * dh
-    qkv = (torch.randn(B, T, 3 * inner) * 0.7).to(torch.bfloat16)
+    g = torch.Generator().manual_seed(1000 * T + 10 * dh + raw)
+    qkv = (torch.randn(B, T, 3 * inner, generator=g) * 0.7).to(torch.bfloat16)
     f = qkv.float().requires_grad_()
     if raw:
         q, k, v = f.transpose(1, 2).reshape(B, heads, T, 3 * dh).chunk(3, dim=-1)
@@ -551,7 +553,7 @@ def test_linear_attention(raw, T, heads, dh):
         q, k, v = (f[..., i * inner:(i + 1) * inner].view(B, T, heads, dh).transpose(1, 2) for i in range(3))
     o = _linear_attention(q, k, v)
     o_tok = o.reshape(B, inner, T).transpose(1, 2) if raw else o.transpose(1, 2).reshape(B, T, inner)
-    do = torch.randn_like(o_tok).to(torch.bfloat16).float()
+    do = torch.randn(o_tok.shape, generator=g).to(torch.bfloat16).float()
     o_tok.backward(do)
     og, state = O.linear_attention_fwd(qkv.to(DEV), T, heads, dh, raw)
     _close(og, o_tok.detach())
@@ -569,14 +571,15 @@ def test_cross_attention(linear, Tq, Tk, heads, dh):
     O = ops()
     B = 2
     inner = heads * dh
-    qb = (torch.randn(B, Tq, inner) * 0.7).to(torch.bfloat16)
-    kvb = (torch.randn(B, Tk, 2 * inner) * 0.7).to(torch.bfloat16)
+    g = torch.Generator().manual_seed(1000 * Tq + 10 * Tk + linear)
+    qb = (torch.randn(B, Tq, inner, generator=g) * 0.7).to(torch.bfloat16)
+    kvb = (torch.randn(B, Tk, 2 * inner, generator=g) * 0.7).to(torch.bfloat16)
     qf, kvf = qb.float().requires_grad_(), kvb.float().requires_grad_()
     q = qf.transpose(1, 2).reshape(B, heads, Tq, dh)
     k, v = kvf.transpose(1, 2).reshape(B, heads, Tk, 2 * dh).chunk(2, dim=-1)
     o = _linear_attention(q, k, v) if linear else F.scaled_dot_product_attention(q, k, v)
     o_tok = o.reshape(B, inner, Tq).transpose(1, 2)
-    do = torch.randn_like(o_tok).to(torch.bfloat16).float()
+    do = torch.randn(o_tok.shape, generator=g).to(torch.bfloat16).float()
     o_tok.backward(do)
     eps = 1e-6 if linear else None
     og, saved = O.cross_attention_fwd(qb.to(DEV), kvb.to(DEV), Tq, Tk, heads, dh, eps)
