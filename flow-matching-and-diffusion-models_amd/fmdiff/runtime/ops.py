@@ -360,7 +360,7 @@ def conv(src0, K, wgt, *, src1=None, ks=3, stride=1, pad=1, upsample=False, tran
          out_f32=False,
          accumulate=False, want_stats=False, ep=None, splits=None, force_generic=False, wgt_tiled=None,
          wgt2_tiled=None, gout=None, s2d_tiled=None, gn=None,
-         pro_fold=None) -> Tuple[torch.Tensor, Optional[Stats]]:
+         pro_fold=None, plan_out=None) -> Tuple[torch.Tensor, Optional[Stats]]:
     """Implicit-GEMM conv (see csrc/conv.hip, csrc/conv_halo.hip).  ``pro=(a, b, silu)``, ``ep=(x0, x1, a, b)``.
     ``want_stats``: True = per-channel statistics of the output (a separate fmd_channel_stats pass when the
     kernel cannot emit them); "free" = only when the kernel emits them (else None: Act statistics are then
@@ -377,7 +377,9 @@ def conv(src0, K, wgt, *, src1=None, ks=3, stride=1, pad=1, upsample=False, tran
     and stores ``gn["res"] = (a, b, mean_rstd, t)`` as :func:`gn_fused_apply` returns them; otherwise ``gn`` is
     left without "res" and the caller runs the GroupNorm itself.
     ``s2d_tiled``: :func:`s2d_tile_weights` of the stride-2 conv's weight -- the problem runs on the space-to-depth
-    halo kernel (fmd_conv_s2d; the caller checks :func:`s2d_eligible`), ``wgt`` unused."""
+    halo kernel (fmd_conv_s2d; the caller checks :func:`s2d_eligible`), ``wgt`` unused.
+    ``plan_out``: a list; the ``ConvPlan`` the library answered for this call (what fmd_conv then launches) and the
+    descriptor's split count are appended to it -- for tests that assert the kernel instance they mean to reach."""
     _need_cuda(src0, "conv")
     # 3-D (spatial_dims = 3): NDHWC tensors, cubic kernels; ``out_hw_`` is then (Do, Ho, Wo)
     d3 = src0.dim() == 5
@@ -492,6 +494,8 @@ def conv(src0, K, wgt, *, src1=None, ks=3, stride=1, pad=1, upsample=False, tran
         d.n_tickets = SMALL_TICKETS
     L, plan = _lib.lib(), _lib.ConvPlan()
     _lib.check(L.fmd_conv_plan(C.byref(d), allow, C.byref(plan)), "fmd_conv_plan")
+    if plan_out is not None:
+        plan_out.extend((plan, int(d.splits)))
     if fold is not None and not plan.fold:   # the fold as its own launch
         pro = _fold_now(fold, N, Hs * Ws, C0, C1)
         _clear_fold(d)
