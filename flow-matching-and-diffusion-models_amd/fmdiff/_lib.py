@@ -106,6 +106,12 @@ class GbJob(C.Structure):
 GB_MAX = 64   # FMD_GB_MAX
 
 
+class VqPlan(C.Structure):
+    """Mirror of ``fmd_vq_plan_t``."""
+    _fields_ = [("splits", i32), ("block_rows", i32), ("tile_codes", i32), ("codes_per_split", i32), ("Kpad", i32),
+                ("Dpad", i32), ("finalize_rows", i32)]
+
+
 # name -> argtypes (restype is int32 unless listed in _RESTYPE)
 SIGNATURES = {
     "fmd_conv": [C.POINTER(ConvDesc), p],
@@ -190,8 +196,15 @@ SIGNATURES = {
     "fmd_head_dgrad": [p, p, i32, p, p, p, i32, i32, i32, i32, i32, p, p, p],
     "fmd_head_wgrad_workspace": [i32, i32, i32, i32, i32, i32],
     "fmd_head_wgrad": [p, i32, p, p, p, i32, i32, i32, i32, i32, p, p, p, p],
+    "fmd_vq_plan": [i32, i32, i32, C.POINTER(VqPlan)],
+    "fmd_vq_workspace": [i32, i32, i32],
+    "fmd_vq_prep": [p, i32, i32, p, p, p, p],
+    "fmd_vq_argmin": [p, i32, i32, i32, i32, p, p, p, p, p],
+    "fmd_vq_finalize": [p, i32, i32, i32, i32, i32, p, p, p, p, p, i32, p, p, p],
+    "fmd_vq_stats": [p, i32, p, i32, i32, i32, f32, i32, f32, p, p],
 }
-_RESTYPE = {"fmd_linear_attention_workspace": i64, "fmd_linear_attention_state": i64, "fmd_wgrad_workspace": i64, "fmd_head_wgrad_workspace": i64, "fmd_halo_tiled_size": i64, "fmd_s2d_tiled_size": i64, "fmd_s2d_tiled_size_nd": i64, "fmd_grouped_linear_bwd_workspace": i64}
+_RESTYPE = {"fmd_linear_attention_workspace": i64, "fmd_linear_attention_state": i64, "fmd_wgrad_workspace": i64, "fmd_head_wgrad_workspace": i64, "fmd_halo_tiled_size": i64, "fmd_s2d_tiled_size": i64, "fmd_s2d_tiled_size_nd": i64, "fmd_grouped_linear_bwd_workspace": i64,
+             "fmd_vq_workspace": i64}
 
 _lib = None
 

@@ -1,1 +1,1 @@
-"""Model families with the reference ``src/models`` API (UNets + factory)."""
+"""Model families with the reference ``src/models`` API (UNets, VAEs and their factories)."""

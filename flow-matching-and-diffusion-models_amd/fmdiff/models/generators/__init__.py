@@ -1,3 +1,4 @@
 from .diffusionfactory import DiffusionUNetFactory
+from .vaefactory import VAEFactory
 
-__all__ = ["DiffusionUNetFactory"]
+__all__ = ["DiffusionUNetFactory", "VAEFactory"]

@@ -1,9 +1,11 @@
-"""VAE modules (reference ``src/nn/modules/vae/__init__.py``): encoder, decoder, diagonal Gaussian.
+"""VAE modules (reference ``src/nn/modules/vae/__init__.py``): encoder, decoder, diagonal Gaussian and the
+vector-quantizer codebooks (forward on ``csrc/vq.hip``).
 
-The codebooks and discriminators of the reference (VQ-VAE / GAN training) are outside the hot path
-(DESIGN.md section 7)."""
+The discriminators of the reference and the EMA codebook update (GAN / VQ-VAE training) are outside the hot
+path."""
+from .codebook import VectorQuantizer, VectorQuantizerEMA
 from .decoder import Decoder
 from .encoder import Encoder
 from .reparameterizer import DiagonalGaussian
 
-__all__ = ["Encoder", "Decoder", "DiagonalGaussian"]
+__all__ = ["Encoder", "Decoder", "DiagonalGaussian", "VectorQuantizer", "VectorQuantizerEMA"]

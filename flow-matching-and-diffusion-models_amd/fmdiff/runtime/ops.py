@@ -1383,3 +1383,99 @@ def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step):
     bc2 = 1.0 - beta2 ** step
     _lib.call("fmd_adamw", _p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
               float(wd), float(bc1), float(bc2), stream())
+
+
+# ------------------------------------------------------------------ vector quantizer (csrc/vq.hip)
+@dataclass
+class VQOut:
+    """Outputs of ``vq_quantize``; ``vq_loss`` / ``perplexity`` / ``mse`` are 0-dim views of one device tensor."""
+    zq: torch.Tensor        # fp32 channels-first [N, D, *spatial] = z + (q - z)
+    zq_nhwc: torch.Tensor   # bf16 [N, *spatial, Cpad], channels >= D zero: the decoder's operand
+    vq_loss: torch.Tensor
+    perplexity: torch.Tensor
+    codes: torch.Tensor     # int64 [N, *spatial]
+    hist: torch.Tensor      # int32 [K]
+    mse: torch.Tensor
+
+
+_vq_planes: list = []   # (weakref(codebook), _version, data_ptr, (Eh, El, hn)), most recent last
+_VQ_PLANES_MAX = 8
+
+
+def vq_plan(M: int, K: int, D: int) -> _lib.VqPlan:
+    plan = _lib.VqPlan()
+    if _lib.lib().fmd_vq_plan(M, K, D, C.byref(plan)) != 0:
+        raise NotImplementedError(f"vq_quantize: M={M}, K={K}, D={D} is not supported (1 <= D <= 256)")
+    return plan
+
+
+def vq_codebook_planes(codebook: torch.Tensor):
+    """bf16 planes E_h, E_l [Kpad][Dpad] and hn = |e|^2 / 2 [Kpad] of an fp32 codebook [K][D], cached per tensor
+    object and keyed on its ``(_version, data_ptr)`` like the VAE engine's folded output conv.
+
+    The key sees torch's own in-place writes only.  A codebook rewritten through a raw pointer (as the fused
+    optimizer kernels write parameters) keeps its ``_version``, and the planes are built on the stream current at
+    the first call.  Nothing writes the codebook on this forward-only path; an EMA update kernel (DESIGN.md
+    section 7, next) must bump the version or drop the entry when it writes ``embedding``."""
+    import weakref
+    ver, ptr = codebook._version, codebook.data_ptr()
+    _vq_planes[:] = [e for e in _vq_planes if e[0]() is not None]
+    for e in _vq_planes:
+        if e[0]() is codebook and e[1] == ver and e[2] == ptr:
+            return e[3]
+    K, D = codebook.shape
+    plan = vq_plan(1, K, D)
+    dev = codebook.device
+    Eh = torch.empty((plan.Kpad, plan.Dpad), device=dev, dtype=BF16)
+    El = torch.empty((plan.Kpad, plan.Dpad), device=dev, dtype=BF16)
+    hn = torch.empty((plan.Kpad,), device=dev, dtype=F32)
+    _lib.call("fmd_vq_prep", _p(codebook), K, D, _p(Eh), _p(El), _p(hn), stream())
+    _vq_planes[:] = [e for e in _vq_planes if e[0]() is not codebook][-(_VQ_PLANES_MAX - 1):]
+    _vq_planes.append((weakref.ref(codebook), ver, ptr, (Eh, El, hn)))
+    return Eh, El, hn
+
+
+def vq_quantize(z_flat, D: int, codebook, beta: float, classic: bool, plan_out=None, *, eps: float = 1e-5,
+                Cpad: Optional[int] = None, out: Optional[dict] = None) -> VQOut:
+    """Nearest-code quantisation of ``z_flat`` (fp32 channels-last ``[N, *spatial, ldz]``, the first ``D``
+    channels of every vector) against the fp32 ``codebook`` [K][D]; see ``VQOut``.  ``plan_out``: a list that
+    receives the launch plan (``_lib.VqPlan``).  ``out``: optional preallocated ``zq`` / ``zq_nhwc`` / ``codes`` /
+    ``hist`` (zeroed) / ``stats`` tensors.  Nothing synchronises with the host."""
+    _need_cuda(z_flat, "vq_quantize")
+    _need_cuda(codebook, "vq_quantize")
+    if z_flat.dtype != F32 or codebook.dtype != F32 or not z_flat.is_contiguous() or not codebook.is_contiguous():
+        raise RuntimeError("vq_quantize: contiguous fp32 tensors")
+    if z_flat.dim() < 2 or codebook.dim() != 2 or codebook.shape[1] != D or z_flat.shape[-1] < D:
+        raise RuntimeError(f"vq_quantize: z [..., >= {D}] against a codebook [K, {D}], got {tuple(z_flat.shape)} "
+                           f"and {tuple(codebook.shape)}")
+    N, sp, ldz = z_flat.shape[0], tuple(z_flat.shape[1:-1]), z_flat.shape[-1]
+    HW = 1
+    for v in sp:
+        HW *= v
+    M, K = N * HW, codebook.shape[0]
+    plan = vq_plan(M, K, D)
+    if plan_out is not None:
+        plan_out.append(plan)
+    dev = z_flat.device
+    Eh, El, hn = vq_codebook_planes(codebook)
+    Cpad = Cpad or max(8, -(-D // 8) * 8)
+    out = out or {}
+    nslab = -(-M // plan.finalize_rows)
+    ws = torch.empty((int(_lib.lib().fmd_vq_workspace(M, K, D)),), device=dev, dtype=torch.uint8)
+    codes = out["codes"] if "codes" in out else torch.empty((N, *sp), device=dev, dtype=torch.int64)
+    zq = out["zq"] if "zq" in out else torch.empty((N, D, *sp), device=dev, dtype=F32)
+    zq_nhwc = out["zq_nhwc"] if "zq_nhwc" in out else torch.empty((N, *sp, Cpad), device=dev, dtype=BF16)
+    hist = out["hist"] if "hist" in out else torch.zeros((K,), device=dev, dtype=torch.int32)
+    stats = out["stats"] if "stats" in out else torch.empty((3,), device=dev, dtype=F32)
+    if (tuple(codes.shape) != (N, *sp) or tuple(zq.shape) != (N, D, *sp) or tuple(zq_nhwc.shape) != (N, *sp, Cpad)
+            or hist.numel() != K or stats.numel() != 3
+            or not all(t.is_contiguous() for t in (codes, zq, zq_nhwc, hist, stats))):
+        raise RuntimeError("vq_quantize: preallocated outputs of the wrong shape")
+    slab = torch.empty((nslab,), device=dev, dtype=F32)
+    s = stream()
+    _lib.call("fmd_vq_argmin", _p(z_flat), ldz, M, K, D, _p(Eh), _p(El), _p(hn), _p(ws), s)
+    _lib.call("fmd_vq_finalize", _p(z_flat), ldz, M, HW, K, D, _p(codebook), _p(ws), _p(codes), _p(zq), _p(zq_nhwc),
+              Cpad, _p(slab), _p(hist), s)
+    _lib.call("fmd_vq_stats", _p(slab), nslab, _p(hist), K, M, D, float(beta), int(bool(classic)), float(eps),
+              _p(stats), s)
+    return VQOut(zq, zq_nhwc, stats[0], stats[1], codes, hist, stats[2])

@@ -1,4 +1,5 @@
-"""Fused HIP execution of the AutoencoderKL encoder / decoder (config D: encode -> denoise -> decode).
+"""Fused HIP execution of the AutoencoderKL / VQVAE encoder and decoder (config D: encode -> denoise -> decode;
+VQVAE: encoder -> HIP quantizer -> decoder, ``vq_forward``).
 
 Walks the reference module trees (``src/nn/modules/vae/encoder.py:139-158``,
 ``decoder.py:133-160``, ``src/models/vae/kl.py:116-128``) with the UNet engine's layer
@@ -44,7 +45,7 @@ class VAEEngine(UNetEngine):
 
     def _stage(self, x):
         """NCHW fp32 -> NHWC bf16 with CPAD-padded channels."""
-        ops._need_cuda(x, "AutoencoderKL")
+        ops._need_cuda(x, type(self.m).__name__)
         Cp = max(CPAD, -(-x.shape[1] // 8) * 8)
         return ops.noise_prepare(None, x.float().contiguous(), None, None, None, Cp)
 
@@ -105,14 +106,19 @@ class VAEEngine(UNetEngine):
             self._fold_key = key
         return self._fold
 
-    @torch.no_grad()
-    def encode_moments(self, x):
-        """AutoencoderKL.encode up to the DiagonalGaussian parameters: NCHW fp32 -> [B, 2*embed_dim, h, w]."""
+    def _encode_nhwc(self, x):
+        """Encoder + folded quant_conv: (fp32 NHWC [B, h, w, Kp], the valid channel count)."""
         vae = self.m
         h, ctx = self._encoder_trunk(vae.encoder, x)
         fold = self._folded_out(vae)
-        out = self.head(vae.encoder.norm_out, fold, h, ctx)
-        return ops.nhwc_to_nchw(out, fold.out_channels)
+        return self.head(vae.encoder.norm_out, fold, h, ctx), fold.out_channels
+
+    @torch.no_grad()
+    def encode_moments(self, x):
+        """AutoencoderKL.encode up to the DiagonalGaussian parameters: NCHW fp32 -> [B, 2*embed_dim, h, w]
+        (VQVAE.encode: the quantizer's input [B, embed_dim, h, w])."""
+        out, K = self._encode_nhwc(x)
+        return ops.nhwc_to_nchw(out, K)
 
     @torch.no_grad()
     def decoder_forward(self, z):
@@ -123,16 +129,30 @@ class VAEEngine(UNetEngine):
 
     @torch.no_grad()
     def decode(self, z):
-        """AutoencoderKL.decode (denorm handled by the caller): post_quant_conv, then the decoder."""
+        """AutoencoderKL.decode / VQVAE.decode (denorm handled by the caller): post_quant_conv, then the decoder."""
+        return self._decode_staged(self._stage(z))
+
+    def _decode_staged(self, zin):
+        """post_quant_conv + decoder from the staged latent (NHWC bf16, CPAD-padded channels)."""
         vae = self.m
         dec, pq = vae.decoder, vae.post_quant_conv.conv
-        zin = self._stage(z)
         Kp = max(CPAD, -(-pq.out_channels // 8) * 8)
         hz, _ = ops.conv(zin, Kp, self.wc.get(pq.weight, 0, Kp, zin.shape[-1]), ks=1, pad=0,
                          bias=self.wc.padded(pq.bias, Kp))
-        ctx = self._ctx(dec, z.shape[0], z.device)
+        ctx = self._ctx(dec, zin.shape[0], zin.device)
         out = self._decoder_trunk(dec, Act(hz, need_grad=False), ctx)
         return ops.nhwc_to_nchw(out, dec.conv_out.conv.out_channels)
+
+    @torch.no_grad()
+    def vq_forward(self, x):
+        """VQVAE.forward: encoder -> quantizer -> post_quant_conv -> decoder.  The quantizer reads the head's
+        fp32 NHWC output in place and writes the decoder's staged operand itself (the bf16 rounding of z_q that
+        ``_stage`` would make), so ``rec`` equals ``decode(codebook(encode(x))[0])`` bit for bit.  Returns
+        (rec NCHW fp32, ops.VQOut)."""
+        vae = self.m
+        quant_in, D = self._encode_nhwc(x)
+        q = vae.codebook.quantize_nhwc(quant_in, Cpad=max(CPAD, -(-D // 8) * 8))
+        return self._decode_staged(q.zq_nhwc), q
 
 
 def get_vae_engine(module) -> VAEEngine:

@@ -606,6 +606,44 @@ int fmd_counter_add(int32_t* c, int32_t v, fmd_stream_t s);
 int fmd_affine_channels(const void* x, int32_t C, int32_t Cpad, int64_t npix, float scale, float shift, void* y,
                         fmd_stream_t s);
 
+/* ------------------------------------------------------------- vector quantizer
+ * Forward of VectorQuantizer / VectorQuantizerEMA (src/nn/modules/vae/codebook.py:67-84, :109-137) without
+ * the M x K distance and one-hot matrices (csrc/vq.hip).  z: M latent vectors of D <= 256 fp32 values with
+ * row stride ldz (an NHWC tensor with padded channels); E: the fp32 codebook [K][D].  The nearest code
+ * maximises z.e_k - 0.5 |e_k|^2, computed from two bf16 planes per operand (three MFMA products, fp32
+ * accumulation) with 0.5 |e_k|^2 in fp32; the lowest index wins equal scores.  Unsupported shapes (D > 256,
+ * M or K < 1 or > 2^30) return -1.
+ *
+ * Call order: fmd_vq_prep once per codebook value, then fmd_vq_argmin -> fmd_vq_finalize -> fmd_vq_stats.
+ * Nothing synchronises with the host. */
+typedef struct fmd_vq_plan_t {
+  int32_t splits;          /* S: code ranges searched by separate workgroups (grid = row blocks x S) */
+  int32_t block_rows;      /* latent vectors per argmin workgroup */
+  int32_t tile_codes;      /* codes per wave tile */
+  int32_t codes_per_split; /* codes of one split (the last may hold fewer) */
+  int32_t Kpad, Dpad;      /* plane dims: Eh / El are bf16 [Kpad][Dpad], hn is fp32 [Kpad] */
+  int32_t finalize_rows;   /* latent vectors per finalize workgroup: slab holds ceil(M / finalize_rows) floats */
+} fmd_vq_plan_t;
+/* What fmd_vq_argmin / fmd_vq_finalize will launch for this shape; Kpad and Dpad do not depend on M. */
+int fmd_vq_plan(int32_t M, int32_t K, int32_t D, fmd_vq_plan_t* out);
+/* Bytes of the argmin workspace: best score fp32 [S][M], then index int32 [S][M].  Negative: unsupported. */
+int64_t fmd_vq_workspace(int32_t M, int32_t K, int32_t D);
+/* Codebook planes: E = Eh + El (bf16, zero padded to [Kpad][Dpad]); hn[k] = 0.5 |e_k|^2 summed over
+ * d = 0 .. D-1 in order, +inf for k >= K. */
+int fmd_vq_prep(const float* E, int32_t K, int32_t D, void* Eh, void* El, float* hn, fmd_stream_t s);
+int fmd_vq_argmin(const float* z, int32_t ldz, int32_t M, int32_t K, int32_t D, const void* Eh, const void* El,
+                  const float* hn, void* ws, fmd_stream_t s);
+/* Merges the splits; codes int64 [M]; zq fp32 channels-first [M / HW][D][HW] = z + (q - z), every operation
+ * rounded on its own (codebook.py:41); zq_nhwc (optional) bf16 [M][Cpad], channels >= D zero; slab: one
+ * partial sum of (q - z)^2 per finalize workgroup; hist int32 [K], zeroed by the caller, += code counts. */
+int fmd_vq_finalize(const float* z, int32_t ldz, int32_t M, int32_t HW, int32_t K, int32_t D, const float* E,
+                    const void* ws, int64_t* codes, float* zq, void* zq_nhwc, int32_t Cpad, float* slab,
+                    int32_t* hist, fmd_stream_t s);
+/* out[0] = vq_loss = (classic ? 1 + beta : beta) * mse (forward value of codebook.py:79-81 / :133-134),
+ * out[1] = perplexity = exp(-sum p log(p + eps)), p = hist / M (codebook.py:52-53), out[2] = mse. */
+int fmd_vq_stats(const float* slab, int32_t nslab, const int32_t* hist, int32_t K, int32_t M, int32_t D, float beta,
+                 int32_t classic, float eps, float* out, fmd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
