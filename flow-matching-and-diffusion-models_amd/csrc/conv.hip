@@ -16,6 +16,7 @@
 // data gradients (transposed gather).
 #include <cstdlib>
 #include "halo_args.h"
+#include "splitk_combine.h"
 
 namespace {
 
@@ -307,33 +308,25 @@ __global__ __launch_bounds__(256, 2) void conv_igemm(const KArgs A) {
   const int K = d.K;
   if constexpr (!GNA) {
   if (d.splits > 1 && d.tickets) {
-    // Split-K combined inside the launch (the protocol of csrc/conv_halo9.hip / conv_small.hip: MI355X_MICROARCH.md,
-    // inter-workgroup visibility, a counter hand-off with a write-through payload).  Each part stores its
-    // accumulators in their register layout (16-byte pieces [part][i][j][thread] of the tile's slab of d.ws, sc1),
-    // drains, one lane takes the tile's ticket; the part drawing the last one resets it, sums the parts in part order
-    // (its own from registers) and runs the unsplit epilogue below.  The launcher admits whole tiles only.
+    // Split-K combined inside the launch (splitk_combine.h).  Each part stores its accumulators in their register
+    // layout (16-byte pieces [part][i][j][thread] of the tile's slab of d.ws); the reducer sums the parts in part
+    // order (its own from registers) and runs the unsplit epilogue below.  The launcher admits whole tiles only.
     constexpr int SLOT = TM * TN * 4;   // floats per thread and part
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc(d.ws + (size_t)b * d.splits * NT * SLOT, 0,
-                                                      d.splits * NT * SLOT * 4, 0x00020000);
+    const auto rs = combine_slab(d.ws + (size_t)b * d.splits * NT * SLOT, d.splits * NT * SLOT * 4);
     auto piece = [&](int s, int i, int j) { return (((s * TM + i) * TN + j) * NT + tid) * 16; };
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rs, piece(split, i, j), 0, 16);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int* const last = (int*)lds;   // the staging buffers are dead after the main loop; the epilogue does not use them
-    if (tid == 0) {
-      auto* tk = (__attribute__((address_space(1))) unsigned*)(d.tickets + b);
-      const unsigned t = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int is_last = t == (unsigned)(d.splits - 1);
-      if (is_last) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *last = is_last;
-    }
+      for (int j = 0; j < TN; ++j) combine_store(rs, piece(split, i, j), __builtin_bit_cast(u32x4, acc[i][j]));
+    // combine_is_last() written out from its pieces: with the flag, a word of this kernel's static LDS array, stored
+    // inside the helper, hipcc assigns conv_igemm's registers differently throughout.  The flag: the staging buffers
+    // are dead after the main loop; the epilogue does not use them
+    int* const last = (int*)lds;
+    combine_drain();
+    if (tid == 0) *last = combine_ticket(d.tickets, b, d.splits);
     __syncthreads();
     if (!*last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    combine_acquire();
     f32x4 tot[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -351,7 +344,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm(const KArgs A) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int j = 0; j < TN; ++j) v[i][j] = __builtin_amdgcn_raw_buffer_load_b128(rs, piece(s, i, j), 0, 16);
+          for (int j = 0; j < TN; ++j) v[i][j] = combine_load(rs, piece(s, i, j));
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll

@@ -19,6 +19,7 @@
 //   channels-last by two more MFMAs against a permuted identity, staged in LDS and stored as 16-byte rows.
 // (The round-4 v9 variants with an LDS weight ring were measured slower and removed in round 5.)
 #include "halo_args.h"
+#include "splitk_combine.h"
 
 namespace {
 
@@ -587,36 +588,23 @@ void conv3x3_halo9b(const HArgs A) {
   };
   if constexpr (THT <= 8 && MODE == 0) {   // (compiled only where its registers fit: the 8- and 4-row 3x3 tiles)
   if (A.splits > 1 && d.tickets) {
-    // Split-K combined inside the launch (MI355X_MICROARCH.md, inter-workgroup visibility: a counter hand-off with a
-    // write-through payload; the same protocol as csrc/conv_small.hip).  Each part stores its accumulators in their
-    // register layout (16-byte pieces [part][pixel block][quarter][thread] of the tile's slab of d.ws) with sc1
-    // stores, every wave drains them, then ONE lane takes the tile's ticket; the part drawing splits - 1 resets it
-    // and sums the parts in part order (its own from registers, the same values it stored), so the result does not
-    // depend on which part arrives last, then runs the unsplit epilogue below.
+    // Split-K combined inside the launch (splitk_combine.h).  Each part stores its accumulators in their register
+    // layout (16-byte pieces [part][pixel block][quarter][thread] of the tile's slab of d.ws); the reducer sums the
+    // parts in part order (its own from registers, the same values it stored), so the result does not depend on
+    // which part arrives last, then runs the unsplit epilogue below.
     constexpr int SLOT = NPB * 16;   // floats per thread and part
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc(d.ws + (size_t)b * A.splits * NT9 * SLOT, 0,
-                                                      A.splits * NT9 * SLOT * 4, 0x00020000);
+    const auto rs = combine_slab(d.ws + (size_t)b * A.splits * NT9 * SLOT, A.splits * NT9 * SLOT * 4);
     auto piece = [&](int s, int pb, int j) { return (((s * NPB + pb) * 4 + j) * NT9 + tid) * 16; };
 #pragma unroll
     for (int pb = 0; pb < NPB; ++pb)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const f32x4 v = f32x4{acc[pb][4 * j], acc[pb][4 * j + 1], acc[pb][4 * j + 2], acc[pb][4 * j + 3]};
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, piece(split, pb, j), 0, 16);
+        combine_store(rs, piece(split, pb, j), __builtin_bit_cast(u32x4, v));
       }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int* const last = (int*)coef;   // the affine table is dead after the chunk loop; the epilogue does not touch it
-    if (tid == 0) {
-      auto* tk = (__attribute__((address_space(1))) unsigned*)(d.tickets + b);
-      const unsigned t = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int is_last = t == (unsigned)(A.splits - 1);
-      if (is_last) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *last = is_last;
-    }
-    __syncthreads();
-    if (!*last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // the flag: the affine table is dead after the chunk loop; the epilogue does not touch it
+    if (!combine_is_last(d.tickets, b, A.splits, (int*)coef)) return;
+    combine_acquire();
     f32x16 tot[NPB];
 #pragma unroll
     for (int pb = 0; pb < NPB; ++pb)
@@ -631,7 +619,7 @@ void conv3x3_halo9b(const HArgs A) {
 #pragma unroll
         for (int pb = 0; pb < NPB; ++pb)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) v[pb * 4 + j] = __builtin_amdgcn_raw_buffer_load_b128(rs, piece(s, pb, j), 0, 16);
+          for (int j = 0; j < 4; ++j) v[pb * 4 + j] = combine_load(rs, piece(s, pb, j));
 #pragma unroll
         for (int pb = 0; pb < NPB; ++pb)
 #pragma unroll

@@ -26,6 +26,7 @@
 // costs ~15 us whatever its size; it replaces three to four launches at the ~5 us floor.
 #include <cstdlib>
 #include "common.h"
+#include "splitk_combine.h"
 #include "../../include/fmdiff.h"
 
 namespace {
@@ -618,39 +619,28 @@ __global__ __launch_bounds__(NT, 512 / NT) void conv_small_kernel(const SArgs A)
     }
   }
   if (A.P > 1) {
-    // Combine of the P parts inside the launch (MI355X_MICROARCH.md, inter-workgroup visibility: a counter hand-off
-    // with write-through payload).  Every part stores its partial tile to its slot of the tile's slab with sc1 stores,
-    // every wave drains them, then ONE lane takes a ticket (relaxed agent-scope add); the part drawing P - 1 is the
-    // reducer: it resets the ticket for the next launch and reads all P slots with sc1 loads, in part order (the sum
-    // does not depend on which part arrives last).
+    // Combine of the P parts inside the launch (splitk_combine.h).  Every part stores its partial tile to its slot of
+    // the tile's slab; the reducer reads all the slots in part order (the sum does not depend on which part arrives
+    // last).
     const int slab_b = A.P * TPX * BC * 4;
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(d.part + (size_t)tile * A.P * TPX * BC, 0, slab_b, 0x00020000);
+    const auto slab = combine_slab(d.part + (size_t)tile * A.P * TPX * BC, slab_b);
     const int eoff = (ep * BC + ej * 8) * 4;
     if (has_eu) {
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o0), rsrc, kp * TPX * BC * 4 + eoff, 0, 16);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o1), rsrc, kp * TPX * BC * 4 + eoff + 16, 0, 16);
+      combine_store(slab, kp * TPX * BC * 4 + eoff, __builtin_bit_cast(u32x4, o0));
+      combine_store(slab, kp * TPX * BC * 4 + eoff + 16, __builtin_bit_cast(u32x4, o1));
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int* last = (int*)(smem + A.off_ab);   // outside the combine scratch
-    if (tid == 0) {
-      auto* tk = (__attribute__((address_space(1))) unsigned*)(d.tickets + tile);
-      const unsigned t = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int is_last = t == (unsigned)(A.P - 1);
-      if (is_last) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *last = is_last;
-    }
-    __syncthreads();
+    // the flag: outside the combine scratch
+    const bool last = combine_is_last((int*)d.tickets, tile, A.P, (int*)(smem + A.off_ab));
     STS(6);
-    if (!*last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (!last) return;
+    combine_acquire();
     if (has_eu) {
       // all 16 slots' loads in flight at once: past the P parts the descriptor's range check returns zeros
       u32x4 v[16][2];
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
-        v[q][0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, q * TPX * BC * 4 + eoff, 0, 16);
-        v[q][1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, q * TPX * BC * 4 + eoff + 16, 0, 16);
+        v[q][0] = combine_load(slab, q * TPX * BC * 4 + eoff);
+        v[q][1] = combine_load(slab, q * TPX * BC * 4 + eoff + 16);
       }
       o0 = f32x4{0.f, 0.f, 0.f, 0.f};
       o1 = f32x4{0.f, 0.f, 0.f, 0.f};

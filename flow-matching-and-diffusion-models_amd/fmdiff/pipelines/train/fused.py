@@ -368,6 +368,7 @@ class FusedTrainStep:
             for _ in range(warmup_iters):
                 self.step(*self._static)
         torch.cuda.current_stream().wait_stream(s)
+        ops.release_combine_workspace(s)   # the warm-up stream is not used again
         for dst, src in zip((self.flat.data, self.m, self.v, self.step_ctr, self.loss_sum), snap):
             dst.copy_(src)
         self.flat.grad.zero_()

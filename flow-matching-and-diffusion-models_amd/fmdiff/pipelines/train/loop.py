@@ -34,6 +34,7 @@ from torch.utils.data import DataLoader
 from torch.utils.data.distributed import DistributedSampler
 
 from ... import utils as U
+from ...runtime import ops
 from ...utils.model_utils import build_diffusion_model, decode_diffusion_batch, prepare_diffusion_visual_batch
 from ..utils import (_prepare_attention_context, build_scheduler, normalize_latent_conditioning,
                      resolve_conditioning_mode)
@@ -99,6 +100,7 @@ def run_training(dataset, json_path, val_dataset=None, resume: Optional[str] = N
         with torch.cuda.stream(work):
             out = _train_loop(dataset, val_dataset, resume, cfg, tr, mblock, objective, step_factory, use_graph, device)
         torch.cuda.current_stream(device).wait_stream(work)
+        ops.release_combine_workspace(work)
         return out
     return _train_loop(dataset, val_dataset, resume, cfg, tr, mblock, objective, step_factory, use_graph, device)
 

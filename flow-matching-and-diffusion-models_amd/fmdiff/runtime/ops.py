@@ -519,7 +519,7 @@ def conv(src0, K, wgt, *, src1=None, ks=3, stride=1, pad=1, upsample=False, tran
         d.stats = _p(slab)
         st = Stats(slab, plan.stats_rows)
     if plan.tickets:
-        d.tickets, d.tickets_rows = _p(_small_workspace(dev)[1]), plan.stats_rows
+        d.tickets, d.tickets_rows = _p(combine_workspace(dev)[1]), plan.stats_rows
     _lib.check(L.fmd_conv(C.byref(d), stream()), "fmd_conv")
     if want_stats is True and st is None:   # "free": only statistics the kernel emits; the consumer derives others
         if ep is not None:
@@ -561,11 +561,56 @@ SMALL_CONV = bool(tuning.get("SMALL_CONV"))
 SMALL_CONV_MAX_HW = tuning.get("SMALL_CONV_MAX_HW")
 SMALL_CONV_MAX_WORK = tuning.get("SMALL_CONV_MAX_WORK")
 SMALL_CONV_SPLIT = tuning.get("SMALL_CONV_SPLIT")
-# the in-launch combine of a split reduction: fp32 partial tiles + arrival tickets, one set per (device, stream) --
-# launches on one stream serialise, so they can share it; the tickets start at zero and every launch leaves them so
+# The in-launch combine of a split reduction (csrc/splitk_combine.h): fp32 partial tiles + arrival tickets.
 SMALL_PART_BYTES = 8 << 20
 SMALL_TICKETS = 4096
-_small_ws = {}
+_combine_ws = {}   # (device index, stream handle) -> (part buffer, tickets); owner: combine_workspace / release_...
+
+
+def combine_workspace(dev):
+    """(part buffer, tickets) of the in-launch combine for the current stream of ``dev``: SMALL_PART_BYTES of fp32
+    parts (fmd_conv_small; fmd_conv's ticketed kernels keep their parts in the conv's own workspace) and
+    SMALL_TICKETS int32 arrival counters, both created together on that stream at first use.  Launches on one stream
+    serialise, so they share one set; the tickets are zero at creation and every completed launch leaves them zero,
+    so nothing fills them again.  (A first use inside a graph capture would record that zero-fill into the graph:
+    ``capture_stream`` creates its entry beforehand.)
+
+    The entry lives until ``release_combine_workspace``.  torch hands out stream handles from a fixed pool per
+    device (32 per priority, plus the default stream), so the dictionary is bounded by that pool, not by the number
+    of ``torch.cuda.Stream`` objects created -- but every pool stream that ever ran a ticketed conv or a split
+    ``conv_small`` keeps its 8 MiB + 16 KiB until released."""
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _combine_ws.get(key)
+    if ws is None:
+        ws = (torch.empty(SMALL_PART_BYTES // 4, device=dev, dtype=F32),
+              torch.zeros(SMALL_TICKETS, device=dev, dtype=torch.int32))
+        _combine_ws[key] = ws
+    return ws
+
+
+def release_combine_workspace(stream):
+    """Drop the combine workspace of ``stream`` (a ``torch.cuda.Stream`` the caller is done with, joined by a
+    ``wait_stream`` or synchronised; the memory goes back to the allocator under that stream, so work still queued
+    on it stays ordered before any reuse).  The capture stream's entry is kept: captured graphs have its pointers
+    baked in, and its handle can come round again in a later ``torch.cuda.Stream()`` (the pool is round-robin).
+    For the same reason the handle of an abandoned stream can be that of another live ``torch.cuda.Stream`` object
+    (a FusedTrainStep's work stream, say) once 32 streams have been created; releasing then drops the live stream's
+    entry too.  That is harmless: launches on the shared handle stay ordered, and the entry is created again, zero
+    tickets included, at that stream's next eager use."""
+    cap = _cap_streams.get(stream.device.index)
+    if cap is None or cap.cuda_stream != stream.cuda_stream:
+        _combine_ws.pop((stream.device.index, stream.cuda_stream), None)
+
+
+# the accessor's name while it was private: the earlier revisions of tests/test_gpu_halo_ticket.py and
+# tests/test_gpu_halo_fold.py read the tickets through it, and they must keep passing on this library
+_small_workspace = combine_workspace
+
+
+def combine_workspace_streams(dev):
+    """The stream handles that hold a combine workspace on ``dev`` (introspection, for tests: nothing in the library
+    calls it)."""
+    return [h for (i, h) in _combine_ws if i == dev.index]
 
 
 _cap_streams = {}
@@ -575,7 +620,14 @@ CAPTURE_STREAM = bool(tuning.get("CAPTURE_STREAM"))
 def capture_stream():
     """The stream graph captures run on: a side stream whose in-launch-combine workspace (tickets zeroed) is created
     before the first capture, so a capture records no fill of it (a fresh per-stream workspace allocated inside the
-    capture would replay its zero-fill every step)."""
+    capture would replay its zero-fill every step).
+
+    Sharing rule: every graph captured on this stream has the same ticket array and part buffer baked in -- a
+    FusedTrainStep's main and bucket graphs, and any sampler captured in the same process, share one workspace.
+    Such graphs must be replayed one after another (on one stream, or ordered by stream waits), never concurrently
+    on two streams: interleaved ticket adds of two launches would leave tiles without a reducer.  FusedTrainStep.replay
+    (its bucket graphs included) and the samplers replay on the caller's current stream, which keeps the rule;
+    nothing checks it."""
     if not CAPTURE_STREAM:
         return None   # torch's own capture stream
     idx = torch.cuda.current_device()
@@ -583,19 +635,9 @@ def capture_stream():
     if s is None:
         s = torch.cuda.Stream(idx)
         with torch.cuda.stream(s):
-            _small_workspace(torch.device("cuda", idx))
+            combine_workspace(torch.device("cuda", idx))
         _cap_streams[idx] = s
     return s
-
-
-def _small_workspace(dev):
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _small_ws.get(key)
-    if ws is None:
-        ws = (torch.empty(SMALL_PART_BYTES // 4, device=dev, dtype=F32),
-              torch.zeros(SMALL_TICKETS, device=dev, dtype=torch.int32))
-        _small_ws[key] = ws
-    return ws
 
 
 def _conv_small_desc(shape0, C1, K, mode, gn, skip, ptrs, split=None):
@@ -674,7 +716,7 @@ def conv_small(src0, K, wgt, *, src1=None, mode="s1", gn=None, src2=None, src3=N
         ptrs.update(st0=_p(gn["st0"].slab), st1=_p(gn["st1"].slab) if gn.get("st1") is not None else None,
                     gamma=_p(gn.get("gamma")), beta=_p(gn.get("beta")), emb=_p(gn.get("emb")))
     skip = (src2.shape[-1], src3.shape[-1] if src3 is not None else 0) if skip_wgt is not None else None
-    part, tickets = _small_workspace(src0.device)
+    part, tickets = combine_workspace(src0.device)
     ptrs.update(part=_p(part), tickets=_p(tickets))
     d, (N, Ho, Wo) = _conv_small_desc(tuple(src0.shape), C1, K, mode, gn, skip, ptrs, split)
     d.bias, d.bias2, d.resid = _p(bias), _p(bias2), _p(resid)

@@ -133,4 +133,4 @@ def test_halo_fold_with_a_declined_ticket_runs_the_two_launch_split(monkeypatch)
     for c, t in ((0, y), (1, y * y)):
         assert ((tot[..., c] - t.sum(1)).abs() <= 1e-5 * t.abs().sum(1) + 1e-6).all(), c
     # no ticket was taken: the workspace stays zero
-    assert int(ops._small_workspace(got.device)[1].abs().sum()) == 0
+    assert int(ops.combine_workspace(got.device)[1].abs().sum()) == 0

@@ -82,7 +82,7 @@ def test_halo_ticket_combine_matches_combine_launch(name, monkeypatch):
     for c, t in ((0, y), (1, q)):
         assert ((tot[..., c] - t.sum(1)).abs() <= 1e-5 * t.abs().sum(1) + 1e-6).all(), (name, c)
     # the tickets are left at zero for the next launch
-    assert int(O._small_workspace(a.device)[1].abs().sum()) == 0
+    assert int(O.combine_workspace(a.device)[1].abs().sum()) == 0
 
 
 def test_halo_ticket_combine_under_uneven_load(monkeypatch):
@@ -165,7 +165,7 @@ def test_split_ticket_combine_implicit_gemm(name, monkeypatch):
         tot = sa.slab.double().reshape(N, -1, K_out, 2).sum(1)
         for c, t in ((0, y), (1, q)):
             assert ((tot[..., c] - t.sum(1)).abs() <= 1e-5 * t.abs().sum(1) + 1e-6).all(), (name, c)
-    assert int(O._small_workspace(a.device)[1].abs().sum()) == 0
+    assert int(O.combine_workspace(a.device)[1].abs().sum()) == 0
 
 
 # problems whose 8-row halo grid is under one round of the chip: 4-row tiles (fmd_halo_set_th4_max_workgroups)
@@ -203,3 +203,64 @@ def test_halo_4row_tiles_match_8row(name, monkeypatch):
     ta = sa.slab.double().reshape(N, -1, K, 2).sum(1)
     tb = sb.slab.double().reshape(N, -1, K, 2).sum(1)
     assert torch.allclose(ta, tb, rtol=1e-12, atol=1e-9), name
+
+
+def test_combine_workspace_released_and_recreated(monkeypatch):
+    """The combine workspace has one owner (ops.combine_workspace / release_combine_workspace): a side stream's entry
+    appears with its first ticketed launches, goes when the stream is released, and a fresh one (new part buffer,
+    tickets zero at creation) reproduces the results bit for bit and is left with every ticket zero."""
+    from fmdiff.runtime import ops as O
+    monkeypatch.setattr(O, "HALO_TICKET", True)
+    x0, w, kw, (N, H, C, K) = _args("latent32_skip", O)
+    # the smallest conv_small problem whose plan splits (tests/test_gpu_conv_small.py)
+    g = torch.Generator().manual_seed(11)
+    s0, s1 = (torch.randn(8, 2, 2, 512, generator=g).to(DEV).to(torch.bfloat16) for _ in range(2))
+    ws = O.prep_weights((torch.randn(512, 1024, 3, 3, generator=g) / 96).to(DEV), 0)
+    assert O.conv_small_ok((8, 2, 2, 512), 512, C1=512, split=0)
+    assert O.conv_small_split((8, 2, 2, 512), 512, C1=512, split=0) > 1
+    dev = x0.device
+    side = torch.cuda.Stream()
+    cap = O.capture_stream()   # its entry is never released: take another stream of the pool if the handles meet
+    if cap is not None and side.cuda_stream == cap.cuda_stream:
+        side = torch.cuda.Stream()
+
+    def run():
+        plan = []
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            a, sa = O.conv(x0, K, w, want_stats=True, plan_out=plan, **kw)
+            b, sb = O.conv_small(s0, 512, ws, src1=s1, split=0)
+        side.synchronize()
+        assert plan[0].tickets == 1
+        return a, sa.slab, b, sb.slab
+
+    first = run()
+    assert side.cuda_stream in O.combine_workspace_streams(dev)
+    O.release_combine_workspace(side)
+    assert side.cuda_stream not in O.combine_workspace_streams(dev)
+    again = run()
+    for u, v in zip(first, again):
+        assert torch.equal(u, v)
+    with torch.cuda.stream(side):
+        tickets = O.combine_workspace(dev)[1]
+    assert int(tickets.abs().sum()) == 0
+
+
+def test_capture_keeps_no_workspace_of_its_warmup_stream(golden):
+    """FusedTrainStep.capture releases the workspace of the warm-up stream it creates: a second capture leaves as
+    many entries on the device as the first."""
+    from fmdiff.models.generators import DiffusionUNetFactory
+    from fmdiff.pipelines.train.fused import FusedTrainStep
+    from fmdiff.runtime import ops as O
+    T, M = golden
+    meta = M["ldct_fm_test"]
+    tr_cfg = meta["training"]
+    x, cond = T["ldct_fm_test/x"].to(DEV), T["ldct_fm_test/cond"].to(DEV)
+    model = DiffusionUNetFactory().build(meta["unet"], tr_cfg["conditioning"], tr_cfg["channels"] or 1).to(DEV)
+    tr = FusedTrainStep(model, lr=1e-3, warmup=0, total_steps=100)
+    counts = []
+    for _ in range(2):
+        tr.capture(x.clamp(0, 1), cond, warmup_iters=1)
+        torch.cuda.synchronize()
+        counts.append(len(O.combine_workspace_streams(x.device)))
+    assert counts[1] == counts[0], counts
