@@ -1521,3 +1521,56 @@ def vq_quantize(z_flat, D: int, codebook, beta: float, classic: bool, plan_out=N
     _lib.call("fmd_vq_stats", _p(slab), nslab, _p(hist), K, M, D, float(beta), int(bool(classic)), float(eps),
               _p(stats), s)
     return VQOut(zq, zq_nhwc, stats[0], stats[1], codes, hist, stats[2])
+
+
+# ------------------------------------------------------------------ image metrics (csrc/metrics.hip)
+@dataclass
+class ImageMetrics:
+    """Per-image outputs of ``image_metrics``: fp64 ``[N]`` views of one ``[3, N]`` device tensor (``stacked``)."""
+    mse: torch.Tensor
+    psnr: torch.Tensor
+    ssim: torch.Tensor
+    stacked: torch.Tensor
+
+
+def image_metrics(gen: torch.Tensor, tgt: torch.Tensor, clamp: bool = True, *, out: Optional[torch.Tensor] = None,
+                  ws: Optional[torch.Tensor] = None) -> ImageMetrics:
+    """MSE, PSNR and SSIM (skimage's defaults: 7-wide uniform window, sample covariance, data_range 1) of every
+    image of two fp32 channels-first batches ``[N, C, H, W]`` or ``[N, C, D, H, W]``, all in fp64 on the device.
+    ``clamp`` clamps both to [0, 1] first (the diffusion evaluate); the autoencoder evaluate passes False.
+    ``[N, C, L]`` signals get ``mse`` and ``psnr`` and NaN in ``ssim`` (the reference skips channels with fewer
+    than two dimensions).  ``out``: optional fp64 ``[3, N]``; ``ws``: optional uint8 workspace of at least
+    ``fmd_image_metrics_workspace`` bytes.  Nothing synchronises with the host."""
+    if tuple(gen.shape) != tuple(tgt.shape):
+        raise ValueError(f"image_metrics: shape mismatch, {tuple(gen.shape)} against {tuple(tgt.shape)}")
+    if gen.dim() >= 6:
+        raise NotImplementedError(f"image_metrics: {gen.dim() - 2} spatial axes (1 to 3 are built)")
+    if gen.dim() < 3:
+        raise ValueError(f"image_metrics: channels-first batches [N, C, *spatial], got {tuple(gen.shape)}")
+    N, Cc = int(gen.shape[0]), int(gen.shape[1])
+    sp = tuple(int(v) for v in gen.shape[2:])
+    if len(sp) >= 2 and min(sp) < 7:
+        raise ValueError("win_size exceeds image extent. Either ensure that your images are at least 7x7; or pass "
+                         f"win_size explicitly (image_metrics has the 7-wide window only); got {sp}")
+    if N < 1 or Cc < 1 or min(sp) < 1:
+        raise ValueError(f"image_metrics: empty batch {tuple(gen.shape)}")
+    _need_cuda(gen, "image_metrics")
+    _need_cuda(tgt, "image_metrics")
+    if gen.dtype != F32 or tgt.dtype != F32 or not gen.is_contiguous() or not tgt.is_contiguous():
+        raise RuntimeError("image_metrics: contiguous fp32 tensors")
+    D, H, W = (0,) * (3 - len(sp)) + sp   # an absent axis is 0
+    need = int(_lib.lib().fmd_image_metrics_workspace(N, Cc, D, H, W))
+    if need < 0:
+        raise NotImplementedError(f"image_metrics: shape {tuple(gen.shape)} is beyond the kernel's grid")
+    dev = gen.device
+    if ws is None:
+        ws = torch.empty((need,), device=dev, dtype=torch.uint8)
+    elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or ws.data_ptr() % 8:
+        raise RuntimeError(f"image_metrics: workspace of at least {need} bytes, 8-byte aligned")
+    if out is None:
+        out = torch.empty((3, N), device=dev, dtype=torch.float64)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (3, N) or not out.is_contiguous():
+        raise RuntimeError(f"image_metrics: out must be contiguous fp64 [3, {N}]")
+    _lib.call("fmd_image_metrics", _p(gen), _p(tgt), N, Cc, D, H, W, int(bool(clamp)), _p(ws), _p(out[0]),
+              _p(out[1]), _p(out[2]), stream())
+    return ImageMetrics(out[0], out[1], out[2], out)

@@ -1,6 +1,7 @@
 """``build_vae_model`` (reference ``src/utils/model_utils/vae_utils.py:14-51``): full config dict -> VAE on the
 device through ``VAEFactory``, optional checkpoint.  Checkpoints are read with ``weights_only=True`` only.  The
-batch encode / decode helpers of the reference live in ``fmdiff.pipelines.latent``."""
+batch encode / decode helpers of the reference live in ``fmdiff.pipelines.latent``; ``reconstruct_vae_batch``
+(``:88-105``), the evaluate mode's encode + decode, is here."""
 from __future__ import annotations
 
 import contextlib
@@ -44,3 +45,16 @@ def build_vae_model(cfg: dict, device: torch.device, ckpt_path=None, set_eval: b
         if ckpt_path is None and not _config_names_checkpoint(cfg):
             warnings.warn("[VAE] No checkpoint provided. Random initialization.")
     return model
+
+
+def reconstruct_vae_batch(model, inputs: torch.Tensor, recon_type: str = "l1") -> torch.Tensor:
+    """Encode + decode of image-space inputs in [0, 1], back in image space (reference ``vae_utils.py:88-105``):
+    ``image_to_model_range`` -> forward with the posterior's mode -> ``raw_output_to_image``.  ``sample_posterior``
+    is passed to the forwards that take it (AutoencoderKL); the VQ models have no posterior to sample."""
+    import inspect
+    x = model.image_to_model_range(inputs)
+    takes = "sample_posterior" in inspect.signature(model.forward).parameters
+    out = model(x, sample_posterior=False) if takes else model(x)
+    if isinstance(out, (list, tuple)):
+        out = out[0]
+    return model.raw_output_to_image(out, recon_type=recon_type)

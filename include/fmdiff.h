@@ -644,6 +644,24 @@ int fmd_vq_finalize(const float* z, int32_t ldz, int32_t M, int32_t HW, int32_t 
 int fmd_vq_stats(const float* slab, int32_t nslab, const int32_t* hist, int32_t K, int32_t M, int32_t D, float beta,
                  int32_t classic, float eps, float* out, fmd_stream_t s);
 
+/* ------------------------------------------------------------- image metrics
+ * Per-image MSE, PSNR and SSIM of the evaluate modes (src/pipelines/samplers/diffusion_like.py:251-263,
+ * src/utils/evaluation_utils.py:64-91) in one pass over both tensors (csrc/metrics.hip).  gen / tgt: fp32
+ * contiguous channels-first [N][C][H][W] (D == 0), [N][C][D][H][W], or signals [N][C][W] (D == 0 and H == 0:
+ * no SSIM, ssim[n] = NaN).  clamp != 0 clamps both to [0, 1] first, as torch.clamp does (NaN stays NaN).
+ *   mse[n]  = mean over the image of (g - t)^2
+ *   psnr[n] = 10 log10(1 / max(mse, 1e-12)); 120 for an exact match
+ *   ssim[n] = mean over channels and window positions of skimage's structural_similarity defaults: uniform
+ *             7-wide window over every spatial axis, sample covariance, C1 = 1e-4, C2 = 9e-4, the positions
+ *             whose whole window lies inside the image (3 cropped from every side)
+ * All arithmetic is fp64 and every sum has a fixed order (no atomics): an image's numbers do not depend on N
+ * or on its place in the batch, and a NaN reaches its own image only.  ws: fmd_image_metrics_workspace bytes
+ * of partials.  A spatial side below 7, C < 1, N < 1 or a grid beyond 2^31 - 1 workgroups: -1 from both.
+ * Nothing synchronises with the host. */
+int64_t fmd_image_metrics_workspace(int32_t N, int32_t C, int32_t D, int32_t H, int32_t W);
+int fmd_image_metrics(const float* gen, const float* tgt, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
+                      int32_t clamp, void* ws, double* mse, double* psnr, double* ssim, fmd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
