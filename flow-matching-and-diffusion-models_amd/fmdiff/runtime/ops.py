@@ -779,21 +779,25 @@ def _head_dims(h):
     return tuple(h.shape)
 
 
-def head_fwd(h, pro, w, bias, K, Kp=8):
-    """out fp32 channels-last [..., Kp] = conv3x3(x3)(SiLU(a*h+b)) for the first K channels (csrc/head.hip)."""
+def head_fwd(h, pro, w, bias, K, Kp=8, out=None):
+    """out fp32 channels-last [..., Kp] = conv3x3(x3)(SiLU(a*h+b)) for the first K channels (csrc/head.hip);
+    ``out``: the buffer to write instead of a new one."""
     _need_cuda(h, "head_fwd")
     N, D, H, W, Cc = _head_dims(h)
-    out = torch.empty((*h.shape[:-1], Kp), device=h.device, dtype=F32)
+    if out is None:
+        out = torch.empty((*h.shape[:-1], Kp), device=h.device, dtype=F32)
     _lib.call("fmd_head_fwd", _p(h), N, D, H, W, Cc, _p(pro[0]), _p(pro[1]), _p(w.contiguous()), _p(bias), K,
               _p(out), stream())
     return out
 
 
-def head_dgrad(dpred, w, K, h, pro):
-    """(dz bf16 channels-last, Stats(sum dz, sum dz*h)) of the head conv (csrc/head.hip)."""
+def head_dgrad(dpred, w, K, h, pro, out=None):
+    """(dz bf16 channels-last, Stats(sum dz, sum dz*h)) of the head conv (csrc/head.hip); ``out``: the (dz, slab)
+    buffers to write instead of new ones."""
     N, D, H, W, Cc = _head_dims(h)
-    dz = torch.empty_like(h)
-    slab = torch.empty((h.numel() // Cc // 64, Cc, 2), device=h.device, dtype=F32)
+    if out is None:
+        out = (torch.empty_like(h), torch.empty((h.numel() // Cc // 64, Cc, 2), device=h.device, dtype=F32))
+    dz, slab = out
     _lib.call("fmd_head_dgrad", _p(dpred), _p(w.contiguous()), K, _p(h), _p(pro[0]), _p(pro[1]), N, D, H, W, Cc,
               _p(dz), _p(slab), stream())
     return dz, Stats(slab, 64)
