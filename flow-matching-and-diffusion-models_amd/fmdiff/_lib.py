@@ -202,6 +202,10 @@ SIGNATURES = {
     "fmd_vq_argmin": [p, i32, i32, i32, i32, p, p, p, p, p],
     "fmd_vq_finalize": [p, i32, i32, i32, i32, i32, p, p, p, p, p, i32, p, p, p],
     "fmd_vq_stats": [p, i32, p, i32, i32, i32, f32, i32, f32, p, p],
+    "fmd_vq_train_plan": [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)],
+    "fmd_vq_ema_update": [p, i32, i32, i32, i32, p, p, f32, f32, f32, f32, p, p, p, p, p, p, p, p],
+    "fmd_vq_codebook_grad": [p, i32, i32, i32, i32, p, p, p, p, f32, p, p],
+    "fmd_vq_backward": [p, i32, i32, i32, i32, p, p, p, i32, p, f32, f32, p, i32, p],
     "fmd_image_metrics_workspace": [i32, i32, i32, i32, i32],
     "fmd_image_metrics": [p, p, i32, i32, i32, i32, i32, i32, p, p, p, p, p],
 }

@@ -1461,8 +1461,8 @@ def vq_codebook_planes(codebook: torch.Tensor):
 
     The key sees torch's own in-place writes only.  A codebook rewritten through a raw pointer (as the fused
     optimizer kernels write parameters) keeps its ``_version``, and the planes are built on the stream current at
-    the first call.  Nothing writes the codebook on this forward-only path; an EMA update kernel (DESIGN.md
-    section 7, next) must bump the version or drop the entry when it writes ``embedding``."""
+    the first call.  ``vq_ema_update`` is the one kernel path that writes a codebook: it rewrites these planes in
+    the same launch, bumps ``embedding._version`` and moves this entry's key along with it."""
     import weakref
     ver, ptr = codebook._version, codebook.data_ptr()
     _vq_planes[:] = [e for e in _vq_planes if e[0]() is not None]
@@ -1525,6 +1525,136 @@ def vq_quantize(z_flat, D: int, codebook, beta: float, classic: bool, plan_out=N
     _lib.call("fmd_vq_stats", _p(slab), nslab, _p(hist), K, M, D, float(beta), int(bool(classic)), float(eps),
               _p(stats), s)
     return VQOut(zq, zq_nhwc, stats[0], stats[1], codes, hist, stats[2])
+
+
+# ------------------------------------------------------------------ quantizer training (csrc/vq_train.hip)
+def _vq_rows(z_flat, D: int, what: str):
+    _need_cuda(z_flat, what)
+    if z_flat.dtype != F32 or not z_flat.is_contiguous() or z_flat.dim() < 2 or z_flat.shape[-1] < D:
+        raise RuntimeError(f"{what}: contiguous fp32 rows [..., >= {D}], got {tuple(z_flat.shape)} {z_flat.dtype}")
+    return z_flat.numel() // z_flat.shape[-1], z_flat.shape[-1]
+
+
+def _vq_state(t, shape, what: str, dtype=F32):
+    _need_cuda(t, what)
+    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{what}: expected a contiguous {dtype} tensor {tuple(shape)}, got {tuple(t.shape)} {t.dtype}")
+
+
+def vq_train_plan(M: int, K: int, D: int):
+    """(codes per workgroup, grid) of the segmented-sum launch."""
+    cpw, grid = C.c_int32(), C.c_int32()
+    if _lib.lib().fmd_vq_train_plan(M, K, D, C.byref(cpw), C.byref(grid)) != 0:
+        raise NotImplementedError(f"vq training kernels: M={M}, K={K}, D={D} is not supported (1 <= D <= 256)")
+    return cpw.value, grid.value
+
+
+def vq_ema_update(z_flat, D: int, codes, hist, embedding, ema_cluster_size, ema_w, decay: float, eps: float,
+                  nsum: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The EMA codebook update of ``VectorQuantizerEMA`` (reference ``codebook.py:120-129``), in place on
+    ``ema_cluster_size`` [K], ``ema_w`` [K, D] and ``embedding`` [K, D], from the latent rows ``z_flat`` (fp32
+    channels-last, the first ``D`` channels), the ``codes`` and the histogram ``hist`` of the ``vq_quantize`` call
+    that used ``embedding``.  Deterministic (fp64 segment sums in row order, no atomics), nothing synchronises.
+
+    The planes ``vq_codebook_planes(embedding)`` caches are rewritten in the same launch and their cache key
+    follows ``embedding._version``, which is bumped: the next ``vq_quantize`` reads the new codebook, also after
+    a graph replay of this call (the replay rewrites the cached buffers; the key it was captured with holds).
+    Returns ``nsum``: the fp64 sum of the new cluster sizes, a one-element device tensor."""
+    M, ldz = _vq_rows(z_flat, D, "vq_ema_update")
+    K = embedding.shape[0]
+    _vq_state(embedding, (K, D), "vq_ema_update")
+    _vq_state(ema_w, (K, D), "vq_ema_update")
+    _vq_state(ema_cluster_size, (K,), "vq_ema_update")
+    _vq_state(hist, (K,), "vq_ema_update", torch.int32)
+    _need_cuda(codes, "vq_ema_update")
+    if codes.dtype != torch.int64 or not codes.is_contiguous() or codes.numel() != M:
+        raise RuntimeError(f"vq_ema_update: codes must be contiguous int64 with {M} elements")
+    vq_train_plan(M, K, D)
+    if nsum is None:
+        nsum = torch.empty((1,), device=z_flat.device, dtype=torch.float64)
+    Eh, El, hn = vq_codebook_planes(embedding)
+    omd = 1 - decay   # in double, as the reference's Python does; rounded to fp32 at the call
+    _lib.call("fmd_vq_ema_update", _p(z_flat), ldz, M, K, D, _p(codes), _p(hist), float(decay), float(omd), float(eps),
+              float(K * eps), _p(ema_cluster_size), _p(ema_w), _p(embedding), _p(Eh), _p(El), _p(hn), _p(nsum),
+              stream())
+    for t in (embedding, ema_w, ema_cluster_size):
+        torch.autograd.graph.increment_version(t)
+    for i, e in enumerate(_vq_planes):
+        if e[0]() is embedding:
+            _vq_planes[i] = (e[0], embedding._version, embedding.data_ptr(), e[3])
+    return nsum
+
+
+_vq_consts: dict = {}
+
+
+def _vq_const(dev, v: float) -> torch.Tensor:
+    key = (str(dev), v)
+    if key not in _vq_consts:
+        _vq_consts[key] = torch.full((1,), v, device=dev, dtype=F32)
+    return _vq_consts[key]
+
+
+def vq_backward(z_flat, D: int, codes, codebook, g_zq, g_loss, c: float, *, out=None) -> torch.Tensor:
+    """Gradient of the quantizer to its input: ``dz = g_zq + g_loss * c * (2 / (M D)) * (z - q)`` on the first
+    ``D`` channels, zero on the padding; ``c`` is beta for the EMA quantizer and beta - 1 for the classic one.
+    ``z_flat`` / ``g_zq`` (or None for zero) / the result are fp32 channels-last with their own row strides;
+    ``g_loss`` is a one-element device tensor or None (zero); ``codebook`` None: ``z_flat`` already holds z - q."""
+    M, ldz = _vq_rows(z_flat, D, "vq_backward")
+    dev = z_flat.device
+    K, ldg = 1, 0
+    if codebook is not None:
+        K = codebook.shape[0]
+        _vq_state(codebook, (K, D), "vq_backward")
+        _need_cuda(codes, "vq_backward")
+        if codes.dtype != torch.int64 or not codes.is_contiguous() or codes.numel() != M:
+            raise RuntimeError(f"vq_backward: codes must be contiguous int64 with {M} elements")
+    if g_zq is not None:
+        Mg, ldg = _vq_rows(g_zq, D, "vq_backward")
+        if Mg != M:
+            raise RuntimeError(f"vq_backward: g_zq has {Mg} rows, z has {M}")
+    if g_loss is None:
+        g_loss = _vq_const(dev, 0.0)
+    _need_cuda(g_loss, "vq_backward")
+    if g_loss.dtype != F32 or g_loss.numel() != 1:
+        raise RuntimeError("vq_backward: g_loss must be one fp32 element")
+    dz = torch.empty_like(z_flat) if out is None else out
+    Mo, lddz = _vq_rows(dz, D, "vq_backward")
+    if Mo != M:
+        raise RuntimeError("vq_backward: preallocated output of the wrong shape")
+    _lib.call("fmd_vq_backward", _p(z_flat), ldz, M, K, D, _p(codes) if codebook is not None else None, _p(codebook),
+              _p(g_zq), ldg, _p(g_loss), float(c), float(2.0 / (M * D)), _p(dz), lddz, stream())
+    return dz
+
+
+def vq_residual(z_flat, D: int, codes, codebook) -> torch.Tensor:
+    """``z - codebook[codes]`` rounded once (padding channels zero): what ``vq_backward`` needs of a codebook that
+    is about to be overwritten by ``vq_ema_update``.  ``fma(1, z - q, 0)`` is exact, so a later
+    ``vq_backward(residual, ..., codebook=None, ...)`` gives the bits of the direct call."""
+    M, _ = _vq_rows(z_flat, D, "vq_residual")
+    r = torch.empty_like(z_flat)
+    _lib.call("fmd_vq_backward", _p(z_flat), z_flat.shape[-1], M, codebook.shape[0], D, _p(codes), _p(codebook), None,
+              0, _p(_vq_const(z_flat.device, 1.0)), 1.0, 1.0, _p(r), r.shape[-1], stream())
+    return r
+
+
+def vq_codebook_grad(z_flat, D: int, codes, hist, codebook, g_loss) -> torch.Tensor:
+    """``g_loss * (2 / (M D)) * (n_k e_k - S_k)`` [K, D]: the codebook term of the VQ-VAE loss, from the same
+    segmented sums as the EMA update (an opt-in deviation: the reference sends the codebook no gradient)."""
+    M, ldz = _vq_rows(z_flat, D, "vq_codebook_grad")
+    K = codebook.shape[0]
+    _vq_state(codebook, (K, D), "vq_codebook_grad")
+    _vq_state(hist, (K,), "vq_codebook_grad", torch.int32)
+    _need_cuda(codes, "vq_codebook_grad")
+    if codes.dtype != torch.int64 or not codes.is_contiguous() or codes.numel() != M:
+        raise RuntimeError(f"vq_codebook_grad: codes must be contiguous int64 with {M} elements")
+    vq_train_plan(M, K, D)
+    if g_loss is None:
+        g_loss = _vq_const(z_flat.device, 0.0)
+    dE = torch.empty_like(codebook)
+    _lib.call("fmd_vq_codebook_grad", _p(z_flat), ldz, M, K, D, _p(codes), _p(hist), _p(codebook), _p(g_loss),
+              float(2.0 / (M * D)), _p(dE), stream())
+    return dE
 
 
 # ------------------------------------------------------------------ image metrics (csrc/metrics.hip)

@@ -644,6 +644,36 @@ int fmd_vq_finalize(const float* z, int32_t ldz, int32_t M, int32_t HW, int32_t 
 int fmd_vq_stats(const float* slab, int32_t nslab, const int32_t* hist, int32_t K, int32_t M, int32_t D, float beta,
                  int32_t classic, float eps, float* out, fmd_stream_t s);
 
+/* Training half (csrc/vq_train.hip), given the codes and the histogram of fmd_vq_finalize.  S_k = the sum of
+ * the latent rows with code k is a segmented sum: a workgroup owns a range of codes, scans the M codes in
+ * ascending row order and adds its rows to fp64 accumulators in that order, so every S_kd is one fp32 rounding
+ * of the exact sum and the same bits on every run.  No atomics, no M x K or K x D temporary, no host
+ * synchronisation.  Only the first D channels of a row are read. */
+/* Host-side query: codes per workgroup and grid of the segmented-sum launch.  Negative: unsupported shape. */
+int fmd_vq_train_plan(int32_t M, int32_t K, int32_t D, int32_t* codes_per_wg, int32_t* grid);
+/* The EMA update of codebook.py:120-129, in place on the three fp32 buffers, every one of the K codes:
+ *   ema_cluster_size_k <- fma(one_minus_decay, n_k, decay * ema_cluster_size_k),   n_k = hist[k];
+ *   n = sum_k ema_cluster_size_k in fp64 (fixed order), rounded to fp32; written to nsum[0] (8 bytes, fp64);
+ *   ema_w_kd <- fma(one_minus_decay, S_kd, decay * ema_w_kd);
+ *   embedding_kd <- ema_w_kd / (((ema_cluster_size_k + eps) / (n + k_eps)) * n),   k_eps = K * eps.
+ * Two launches (cluster sizes and n, then everything else).  Eh / El / hn: the planes of fmd_vq_prep for this
+ * codebook, rewritten for the new embedding with the same arithmetic (all three or none). */
+int fmd_vq_ema_update(const float* z, int32_t ldz, int32_t M, int32_t K, int32_t D, const int64_t* codes,
+                      const int32_t* hist, float decay, float one_minus_decay, float eps, float k_eps,
+                      float* ema_cluster_size, float* ema_w, float* embedding, void* Eh, void* El, float* hn,
+                      double* nsum, fmd_stream_t s);
+/* d_embedding[k][d] = (g_loss[0] * scale) * fma(n_k, embedding_kd, -S_kd): the codebook term of the VQ-VAE
+ * loss (the reference sends no gradient to the codebook; an opt-in deviation).  Written, not accumulated. */
+int fmd_vq_codebook_grad(const float* z, int32_t ldz, int32_t M, int32_t K, int32_t D, const int64_t* codes,
+                         const int32_t* hist, const float* embedding, const float* g_loss, float scale,
+                         float* d_embedding, fmd_stream_t s);
+/* dz[m][d] = fma((g_loss[0] * c) * scale, z_md - embedding[codes_m][d], g_zq[m][d]) for d < D and 0 for
+ * D <= d < lddz; g_zq null: zero.  embedding null: the rows of z already hold z - q (codes is not read).
+ * c = beta (EMA quantizer) or beta - 1 (classic), scale = 2 / (M D); g_loss is a device scalar. */
+int fmd_vq_backward(const float* z, int32_t ldz, int32_t M, int32_t K, int32_t D, const int64_t* codes,
+                    const float* embedding, const float* g_zq, int32_t ldg, const float* g_loss, float c,
+                    float scale, float* dz, int32_t lddz, fmd_stream_t s);
+
 /* ------------------------------------------------------------- image metrics
  * Per-image MSE, PSNR and SSIM of the evaluate modes (src/pipelines/samplers/diffusion_like.py:251-263,
  * src/utils/evaluation_utils.py:64-91) in one pass over both tensors (csrc/metrics.hip).  gen / tgt: fp32
