@@ -6,6 +6,6 @@ path."""
 from .codebook import VectorQuantizer, VectorQuantizerEMA
 from .decoder import Decoder
 from .encoder import Encoder
-from .reparameterizer import DiagonalGaussian
+from .reparameterizer import DiagonalGaussian, reparameterize_kl
 
-__all__ = ["Encoder", "Decoder", "DiagonalGaussian", "VectorQuantizer", "VectorQuantizerEMA"]
+__all__ = ["Encoder", "Decoder", "DiagonalGaussian", "VectorQuantizer", "VectorQuantizerEMA", "reparameterize_kl"]

@@ -1708,3 +1708,213 @@ def image_metrics(gen: torch.Tensor, tgt: torch.Tensor, clamp: bool = True, *, o
     _lib.call("fmd_image_metrics", _p(gen), _p(tgt), N, Cc, D, H, W, int(bool(clamp)), _p(ws), _p(out[0]),
               _p(out[1]), _p(out[2]), stream())
     return ImageMetrics(out[0], out[1], out[2], out)
+
+
+# ------------------------------------------------------------------ VAE criterion (csrc/vae_loss.hip)
+LOSS_TERMS = {"l1": 0, "mse": 1, "bce": 2, "focal": 3, "bce_focal": 4, "hinge_real": 5, "hinge_fake": 6, "neg": 7,
+              "square": 8}
+LOSS_REDUCTIONS = {"none": 0, "sum": 1, "mean": 2}
+VAE_LOSS_CHUNK, VAE_LOSS_ROWS, GAUSS_ROWS = 2048, 512, 256   # FMD_VAE_LOSS_CHUNK / _ROWS, FMD_GAUSS_ROWS
+
+
+@dataclass
+class LossOut:
+    """What one ``elementwise_loss`` launch wrote (None: not asked for)."""
+    loss: Optional[torch.Tensor]      # fp32 scalar
+    elem: Optional[torch.Tensor]      # fp32, the target's shape (the shape of x when flat)
+    dx: Optional[torch.Tensor]        # fp32, x's layout
+    dx_bf16: Optional[torch.Tensor]   # bf16 [N, *spatial, ldb]
+
+
+def _f32c(t, what: str, name: str):
+    _need_cuda(t, what)
+    if t.dtype != F32 or not t.is_contiguous():
+        raise RuntimeError(f"{what}: {name} must be a contiguous fp32 tensor, got {t.dtype}"
+                           f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+
+
+def _ws(ws, need: int, dev, what: str):
+    if ws is None:
+        return torch.empty((max(need, 8),), device=dev, dtype=torch.uint8)
+    if ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or ws.data_ptr() % 8:
+        raise RuntimeError(f"{what}: workspace of at least {need} bytes, 8-byte aligned")
+    return ws
+
+
+def elementwise_loss(term: str, x, target=None, *, reduction: str = "mean", alpha: float = 0.25,
+                     channels: Optional[int] = None, g=None, scale: float = 1.0, loss: bool = True,
+                     grad: bool = False, grad_bf16: bool = False, ldb: Optional[int] = None,
+                     out: Optional[dict] = None, ws=None) -> LossOut:
+    """One launch of the element-wise loss family (``include/fmdiff.h``, "VAE training criterion") over ``x``.
+
+    Flat (``channels=None``): ``x`` and ``target`` are contiguous fp32 of one shape.  Head layout
+    (``channels=C``): ``x`` is channels-last ``[N, *spatial, ld]`` with ``ld >= C`` (channels past ``C`` are never
+    read) and ``target`` channels-first ``[N, C, *spatial]``.  ``loss`` asks for the reduced value (``sum`` /
+    ``mean``) or, with ``reduction="none"``, the per-element term; ``grad`` / ``grad_bf16`` ask for
+    ``g * scale * d term / dx`` in x's layout (fp32) and its bf16 copy ``[N, *spatial, ldb]`` (head layout only),
+    where ``g`` is a device tensor: one element, or for ``reduction="none"`` one per element of the term.
+    ``out``: optional preallocated ``loss`` / ``elem`` / ``dx`` / ``dx_bf16``; ``ws``: optional uint8 workspace.
+    Nothing synchronises with the host."""
+    what = "elementwise_loss"
+    if term not in LOSS_TERMS:
+        raise ValueError(f"{what}: unknown term '{term}'")
+    if reduction not in LOSS_REDUCTIONS:
+        raise ValueError(f"{what}: unknown reduction '{reduction}'")
+    tid, rid = LOSS_TERMS[term], LOSS_REDUCTIONS[reduction]
+    has_t = tid <= 4
+    if has_t and target is None:
+        raise ValueError(f"{what}: term '{term}' needs a target")
+    if not has_t and (target is not None or channels is not None):
+        raise ValueError(f"{what}: term '{term}' takes no target and flat addressing")
+    _f32c(x, what, "x")
+    if has_t:
+        _f32c(target, what, "target")
+    if channels is None:
+        if has_t and tuple(target.shape) != tuple(x.shape):
+            raise ValueError(f"{what}: shape mismatch, x {tuple(x.shape)} against target {tuple(target.shape)}")
+        N, Cc, P, ld = 1, 1, x.numel(), 0
+        tshape = tuple(x.shape)
+        if grad_bf16:
+            raise ValueError(f"{what}: the bf16 gradient copy is written in the head layout only")
+    else:
+        Cc = int(channels)
+        if (x.dim() < 3 or target.dim() != x.dim() or target.shape[1] != Cc or x.shape[-1] < Cc
+                or x.shape[0] != target.shape[0] or tuple(x.shape[1:-1]) != tuple(target.shape[2:])):
+            raise ValueError(f"{what}: head layout wants x [N, *spatial, >= {Cc}] and target [N, {Cc}, *spatial], "
+                             f"got {tuple(x.shape)} and {tuple(target.shape)}")
+        N, ld = int(x.shape[0]), int(x.shape[-1])
+        P = x.numel() // max(1, N * ld)
+        tshape = tuple(target.shape)
+    need = int(_lib.lib().fmd_vae_loss_workspace(tid, N, Cc, P, ld))
+    if need < 0:
+        raise ValueError(f"{what}: empty tensor or a shape beyond the kernel's grid, {tuple(x.shape)}")
+    dev, out = x.device, out or {}
+    want_g = grad or grad_bf16
+    g_elem = 0
+    if want_g:
+        if g is None:
+            raise ValueError(f"{what}: a gradient needs the upstream gradient g (a device tensor)")
+        _f32c(g, what, "g")
+        if g.numel() != 1:
+            if rid != 0 or tuple(g.shape) != tshape:
+                raise ValueError(f"{what}: g must have one element, or the term's shape {tshape} with "
+                                 f"reduction='none'; got {tuple(g.shape)}")
+            g_elem = 1
+
+    def buf(key, shape, dtype):
+        t = out.get(key)
+        if t is None:
+            return torch.empty(shape, device=dev, dtype=dtype)
+        _need_cuda(t, what)
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise RuntimeError(f"{what}: out['{key}'] must be contiguous {dtype} {tuple(shape)}")
+        return t
+
+    o_loss = buf("loss", (), F32) if loss and rid != 0 else None
+    o_elem = buf("elem", tshape, F32) if loss and rid == 0 else None
+    o_dx = buf("dx", tuple(x.shape), F32) if grad else None
+    o_b = None
+    if grad_bf16:
+        ldb = int(ldb or max(8, -(-Cc // 8) * 8))
+        if ldb < Cc:
+            raise ValueError(f"{what}: ldb {ldb} below the channel count {Cc}")
+        o_b = buf("dx_bf16", (*x.shape[:-1], ldb), BF16)
+    if o_loss is None and o_elem is None and not want_g:
+        raise ValueError(f"{what}: nothing asked for")
+    if o_loss is not None:
+        ws = _ws(ws, need, dev, what)
+    _lib.call("fmd_vae_loss", tid, rid, _p(x), _p(target), N, Cc, P, ld, float(alpha), _p(g) if want_g else None,
+              g_elem, float(scale), _p(ws) if o_loss is not None else None, _p(o_loss), _p(o_elem), _p(o_dx),
+              _p(o_b), int(ldb or 0), stream())
+    return LossOut(o_loss, o_elem, o_dx, o_b)
+
+
+def _gauss_dims(moments, E: int, what: str):
+    _f32c(moments, what, "moments")
+    if moments.dim() < 3 or moments.shape[-1] < 2 * E or E < 1:
+        raise ValueError(f"{what}: moments are channels-last [N, *spatial, >= {2 * E}], got {tuple(moments.shape)}")
+    N, ldm = int(moments.shape[0]), int(moments.shape[-1])
+    sp = tuple(int(v) for v in moments.shape[1:-1])
+    P = 1
+    for v in sp:
+        P *= v
+    return N, sp, P, ldm
+
+
+def _gauss_cf(t, shape, what: str, name: str):
+    if t is None:
+        return
+    _f32c(t, what, name)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} must be {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def gauss_sample_kl(moments, E: int, eps=None, *, Cp: Optional[int] = None, out: Optional[dict] = None, ws=None):
+    """Posterior of ``DiagonalGaussian`` in one pass over the channels-last fp32 ``moments`` ``[N, *spatial, >= 2E]``
+    (mu then logvar): ``z = mu + exp(0.5 clamp(logvar, -30, 20)) eps`` channels-first ``[N, E, *spatial]`` (``eps``
+    channels-first of that shape; None: the mode, ``z = mu``), ``kl [N]``, and with ``Cp`` the decoder's staged
+    operand, bf16 ``[N, *spatial, Cp]``.  Returns ``(z, kl, z_staged or None)``.  Nothing synchronises."""
+    what = "gauss_sample_kl"
+    N, sp, P, ldm = _gauss_dims(moments, E, what)
+    _gauss_cf(eps, (N, E, *sp), what, "eps")
+    need = int(_lib.lib().fmd_gauss_workspace(N, E, P))
+    if need < 0:
+        raise ValueError(f"{what}: empty tensor or a shape beyond the kernel's grid, {tuple(moments.shape)}")
+    dev, out = moments.device, out or {}
+
+    def buf(key, shape, dtype):
+        t = out.get(key)
+        if t is None:
+            return torch.empty(shape, device=dev, dtype=dtype)
+        _need_cuda(t, what)
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise RuntimeError(f"{what}: out['{key}'] must be contiguous {dtype} {tuple(shape)}")
+        return t
+
+    z = buf("z", (N, E, *sp), F32)
+    kl = buf("kl", (N,), F32)
+    zs = None
+    if Cp is not None:
+        if Cp < E:
+            raise ValueError(f"{what}: Cp {Cp} below the latent channels {E}")
+        zs = buf("z_staged", (N, *sp, int(Cp)), BF16)
+    ws = _ws(ws, need, dev, what)
+    _lib.call("fmd_gauss_sample_kl", _p(moments), ldm, N, E, P, _p(eps), _p(z), _p(zs), int(Cp or 0), _p(ws), _p(kl),
+              stream())
+    return z, kl, zs
+
+
+def gauss_backward(moments, E: int, eps, g_z, g_kl, *, ldd: Optional[int] = None, ldb: Optional[int] = None,
+                   out: Optional[dict] = None):
+    """Gradient of ``gauss_sample_kl`` to the moments, recomputed from them: fp32 channels-last
+    ``[N, *spatial, ldd]`` (default: the stride of ``moments``) and, with ``ldb``, its bf16 copy; padding channels
+    zero.  ``g_z`` (channels-first like ``z``), ``g_kl`` (``[N]``) and ``eps`` may each be None (zero).  Returns
+    ``(d_moments, d_moments_bf16 or None)``."""
+    what = "gauss_backward"
+    N, sp, P, ldm = _gauss_dims(moments, E, what)
+    _gauss_cf(eps, (N, E, *sp), what, "eps")
+    _gauss_cf(g_z, (N, E, *sp), what, "g_z")
+    _gauss_cf(g_kl, (N,), what, "g_kl")
+    ldd = int(ldd or ldm)
+    if ldd < 2 * E or (ldb is not None and ldb < 2 * E):
+        raise ValueError(f"{what}: output strides below {2 * E} channels")
+    dev, out = moments.device, out or {}
+    dm = out.get("d_moments")
+    if dm is None:
+        dm = torch.empty((N, *sp, ldd), device=dev, dtype=F32)
+    else:
+        _f32c(dm, what, "out['d_moments']")
+        if tuple(dm.shape) != (N, *sp, ldd):
+            raise RuntimeError(f"{what}: out['d_moments'] must be {(N, *sp, ldd)}")
+    db = None
+    if ldb is not None:
+        db = out.get("d_moments_bf16")
+        if db is None:
+            db = torch.empty((N, *sp, int(ldb)), device=dev, dtype=BF16)
+        elif db.dtype != BF16 or tuple(db.shape) != (N, *sp, int(ldb)) or not db.is_contiguous() or not db.is_cuda:
+            raise RuntimeError(f"{what}: out['d_moments_bf16'] must be contiguous bf16 {(N, *sp, int(ldb))}")
+    if int(_lib.lib().fmd_gauss_workspace(N, E, P)) < 0:
+        raise ValueError(f"{what}: empty tensor or a shape beyond the kernel's grid, {tuple(moments.shape)}")
+    _lib.call("fmd_gauss_backward", _p(moments), ldm, N, E, P, _p(eps), _p(g_z), _p(g_kl), _p(dm), ldd, _p(db),
+              int(ldb or 0), stream())
+    return dm, db

@@ -154,6 +154,22 @@ class VAEEngine(UNetEngine):
         q = vae.codebook.quantize_nhwc(quant_in, Cpad=max(CPAD, -(-D // 8) * 8))
         return self._decode_staged(q.zq_nhwc), q
 
+    @torch.no_grad()
+    def kl_forward(self, x, eps=None, sample=True):
+        """AutoencoderKL.forward for training: encoder -> posterior kernel -> post_quant_conv -> decoder.  The
+        posterior kernel (``ops.gauss_sample_kl``) reads the head's fp32 NHWC moments in place, samples (``eps``
+        fp32 ``[B, embed_dim, h, w]``; None: drawn with ``torch.randn``; ``sample=False``: the mode), sums the KL
+        and writes the decoder's staged operand itself (the bf16 rounding of z that ``_stage`` would make), so
+        ``rec`` equals ``decode(z)`` bit for bit.  Returns (rec NCHW fp32, z NCHW fp32, kl [B])."""
+        mom, K = self._encode_nhwc(x)
+        E = K // 2
+        if not sample:
+            eps = None
+        elif eps is None:
+            eps = torch.randn((mom.shape[0], E, *mom.shape[1:-1]), device=mom.device, dtype=F32)
+        z, kl, zs = ops.gauss_sample_kl(mom, E, eps, Cp=max(CPAD, -(-E // 8) * 8))
+        return self._decode_staged(zs), z, kl
+
 
 def get_vae_engine(module) -> VAEEngine:
     eng = getattr(module, "_fmd_vae_engine", None)

@@ -692,6 +692,60 @@ int64_t fmd_image_metrics_workspace(int32_t N, int32_t C, int32_t D, int32_t H, 
 int fmd_image_metrics(const float* gen, const float* tgt, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
                       int32_t clamp, void* ws, double* mse, double* psnr, double* ssim, fmd_stream_t s);
 
+/* ------------------------------------------------------------- VAE training criterion
+ * The losses of VAE training (src/nn/losses/vae.py:104-151, src/pipelines/train/vae_lib.py:226-275, with
+ * raw_output_to_image of src/models/autoencoder/base.py:21-28 fused in) and the posterior of
+ * src/nn/modules/vae/reparameterizer.py:19-47 (csrc/vae_loss.hip).  Inputs are fp32; img = (clamp(x,-1,1) + 1)
+ * * 0.5 is torch's three fp32 operations; everything after it is fp64 (exp / log1p / expm1 included) and every
+ * value written is one rounding of its fp64 value.  Every sum is fp64 in a fixed order (per-workgroup partials
+ * in ws, then a finishing launch): no atomics, the grid is a function of the shape, the same bits on every run.
+ * Nothing synchronises with the host; upstream gradients are device memory.
+ *
+ * term (p = sigma(x), t the target):
+ *   0 l1          |img - t|                          d/dx: sign(img - t) * 0.5 * [-1 <= x <= 1], sign(0) = 0
+ *   1 mse         (img - t)^2                        d/dx: (img - t) * [-1 <= x <= 1]
+ *   2 bce         max(x,0) - x t + log1p(exp(-|x|))  d/dx: p - t
+ *   3 focal       a_t (1 - p_t)^2 ce, 1 - p_t = t sigma(-x) + (1 - t) sigma(x), a_t = alpha t + (1-alpha)(1-t)
+ *                                                    d/dx: a_t [(1-p_t)^2 (p - t) - 2 (1-p_t) p (1-p) (2t-1) ce]
+ *   4 bce_focal   bce + focal
+ *   5 hinge_real  relu(1 - x)  (d/dx = 0 at x = 1)   6 hinge_fake  relu(1 + x)  (d/dx = 0 at x = -1)
+ *   7 neg         -x                                 8 square      x^2
+ * Terms 5 to 8 take no target.  reduction: 0 none, 1 sum, 2 mean.
+ *
+ * Addressing.  ld > 0, head layout (terms 0 to 4): x channels-last [N][P][ld], channels >= C never read (the
+ * decoder head's fp32 output in place); target, g (g_elem != 0) and elem channels-first [N][C][P]; dx
+ * [N][P][ld] and dx_bf16 [N][P][ldb] (the operand of fmd_head_dgrad), channels >= C written as 0.
+ * FMD_VAE_LOSS_ROWS pixels per workgroup.  ld == 0, flat: N = C = 1 and x, target, g, elem, dx are P contiguous
+ * elements; FMD_VAE_LOSS_CHUNK elements per workgroup; no dx_bf16.
+ *
+ * Outputs, each optional (null: not wanted; at least one): loss[0] = fp32 of the fp64 sum (/ N C P for the
+ * mean), which needs ws and reduction != 0; elem = the per-element term; dx = (g * scale [/ N C P for the mean])
+ * * d term / dx with g = g[0], or g[i] per element of the term when g_elem != 0; dx_bf16 = bf16 of dx.
+ * fmd_vae_loss_workspace: bytes of ws (8 per workgroup).  Empty shapes, C > ld, an unknown term, a grid beyond
+ * 2^31 - 1: -1 from both. */
+#define FMD_VAE_LOSS_CHUNK 2048
+#define FMD_VAE_LOSS_ROWS 512
+int64_t fmd_vae_loss_workspace(int32_t term, int32_t N, int32_t C, int64_t P, int32_t ld);
+int fmd_vae_loss(int32_t term, int32_t reduction, const float* x, const float* target, int32_t N, int32_t C,
+                 int64_t P, int32_t ld, float alpha, const float* g, int32_t g_elem, float scale, void* ws,
+                 float* loss, float* elem, float* dx, void* dx_bf16, int32_t ldb, fmd_stream_t s);
+/* Posterior in one pass.  moments fp32 channels-last [N][P][ldm], channels 0 .. E-1 mu and E .. 2E-1 logvar
+ * (the encoder head's output in place); eps fp32 channels-first [N][E][P], null: the mode (z = mu).
+ *   lv = clamp(logvar, -30, 20);  z = mu + exp(0.5 lv) eps  -> z fp32 channels-first [N][E][P];
+ *   z_staged (optional) bf16 channels-last [N][P][Cp], bf16 of z, channels >= E zero (the decoder's operand);
+ *   kl[n] = 0.5 sum_{c,p} (mu^2 + expm1(lv) - lv): FMD_GAUSS_ROWS pixels per workgroup, the partials of sample n
+ *   summed on their own, so kl[n] does not depend on N or on n.  ws: fmd_gauss_workspace bytes. */
+#define FMD_GAUSS_ROWS 256
+int64_t fmd_gauss_workspace(int32_t N, int32_t E, int64_t P);
+int fmd_gauss_sample_kl(const float* moments, int32_t ldm, int32_t N, int32_t E, int64_t P, const float* eps,
+                        float* z, void* z_staged, int32_t Cp, void* ws, float* kl, fmd_stream_t s);
+/* d_mu = g_z + g_kl[n] mu;  d_logvar = [-30 <= logvar <= 20] (g_z eps 0.5 exp(0.5 lv) + g_kl[n] 0.5 expm1(lv)).
+ * g_z fp32 [N][E][P] or null (zero), g_kl fp32 [N] or null (zero), eps null: zero.  d_moments fp32 [N][P][ldd]
+ * and / or d_moments_bf16 [N][P][ldb], channels >= 2E zero. */
+int fmd_gauss_backward(const float* moments, int32_t ldm, int32_t N, int32_t E, int64_t P, const float* eps,
+                       const float* g_z, const float* g_kl, float* d_moments, int32_t ldd, void* d_moments_bf16,
+                       int32_t ldb, fmd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
