@@ -448,9 +448,12 @@ __global__ __launch_bounds__(256, 2) void conv_igemm(const KArgs A) {
         u32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          float lo = Pv[2 * e] * bf_lo(vz[k][e]) + Qv[2 * e] * bf_lo(vx[k][e]) + Rv[2 * e] + bf_lo(ve[e]);
-          float hi = Pv[2 * e + 1] * bf_hi(vz[k][e]) + Qv[2 * e + 1] * bf_hi(vx[k][e]) + Rv[2 * e + 1] +
-                     bf_hi(ve[e]);
+          // the contraction spelled out (fma(P, dz, Q*x), what the plain sum compiled to): csrc/skip_bwd.hip
+          // reproduces these bits, so neither side is left to the compiler's choice
+          float lo = __builtin_fmaf(Pv[2 * e], bf_lo(vz[k][e]), Qv[2 * e] * bf_lo(vx[k][e])) + Rv[2 * e] +
+                     bf_lo(ve[e]);
+          float hi = __builtin_fmaf(Pv[2 * e + 1], bf_hi(vz[k][e]), Qv[2 * e + 1] * bf_hi(vx[k][e])) +
+                     Rv[2 * e + 1] + bf_hi(ve[e]);
           if (accf) { lo += bf_lo(old[k][e]); hi += bf_hi(old[k][e]); }
           o[e] = pack2(lo, hi);
         }

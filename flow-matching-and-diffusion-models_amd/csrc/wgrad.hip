@@ -502,6 +502,14 @@ extern "C" int fmd_wgrad(const fmd_wgrad_desc* d, fmd_stream_t stream) {
     rc = (int)hipGetLastError();
   }
   if (rc) return rc;
+  return fmd_wgrad_combine(d, stream);
+}
+
+extern "C" int fmd_wgrad_combine(const fmd_wgrad_desc* d, fmd_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = check_desc(d)) return rc;
+  WArgs A = make_args(d);
+  const int splits = d->splits > 1 ? d->splits : 1;
   if (A.T > 27) return -4;
   // one pass: wgrad_reduce2 (all taps per block, slabs over slab lanes); wgrad_reduce when C % 4 != 0.  (Round 3's
   // two-stage form -- groups of 8 slabs summed in place, then wgrad_reduce -- was 0.4 ms per train step slower.)

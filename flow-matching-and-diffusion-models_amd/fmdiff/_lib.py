@@ -63,6 +63,18 @@ class GnApplyDesc(C.Structure):
     ]
 
 
+class SkipBwdDesc(C.Structure):
+    """Mirror of ``fmd_skip_bwd_desc``."""
+    _fields_ = [("N", i32), ("HW", i32), ("C0", i32), ("C1", i32), ("Kd", i32), ("dy", p), ("wgt_t", p),
+                ("g", GnApplyDesc), ("dw", p), ("db", p), ("accumulate", i32), ("ws", p), ("groups", i32),
+                ("num_cu", i32), ("min_tiles", i32)]
+
+
+class SkipBwdPlan(C.Structure):
+    """Mirror of ``fmd_skip_bwd_plan_t``."""
+    _fields_ = [("taken", i32), ("c_tile", i32), ("workgroups", i32), ("slabs", i32), ("ws_floats", i64)]
+
+
 class GnOutDesc(C.Structure):
     """Mirror of ``fmd_gn_out_desc``."""
     _fields_ = [("G", i32), ("eps", f32), ("gamma", p), ("beta", p), ("emb", p), ("emb_stride", i32),
@@ -124,6 +136,9 @@ SIGNATURES = {
     "fmd_wgrad_halo": [C.POINTER(WgradDesc), p],
     "fmd_wgrad_group": [C.POINTER(WgradDesc), i32, p],
     "fmd_wgrad_halo_group": [C.POINTER(WgradDesc), i32, p],
+    "fmd_wgrad_combine": [C.POINTER(WgradDesc), p],
+    "fmd_skip_bwd_plan": [C.POINTER(SkipBwdDesc), C.POINTER(SkipBwdPlan)],
+    "fmd_skip_bwd": [C.POINTER(SkipBwdDesc), p],
     "fmd_halo_tiled_size": [i32, i32, i32],
     "fmd_tile_weights_halo": [p, i32, i32, i32, p, p],
     "fmd_conv_s2d": [C.POINTER(ConvDesc), p],

@@ -717,6 +717,11 @@ class UNetEngine:
         if ctx.tape is None:
             return o
 
+        # non-identity skip: where fmd_skip_bwd's plan takes the block, the skip conv's weight and bias gradient
+        # ride in the GroupNorm-1 backward apply pass below instead of a weight-gradient launch of their own
+        skip_fused = (not isinstance(sk, Identity) and sk.conv.bias is not None
+                      and ops.skip_bwd_plan(N, HW, C0, C1, Cout) is not None)
+
         def bwd():
             dy = o.grad
 
@@ -725,7 +730,7 @@ class UNetEngine:
                     ops.wgrad(t2 if t2 is not None else gg2, dy, c2.weight.grad, db=c2.bias.grad)
                 else:
                     ops.wgrad(h, dy, c2.weight.grad, pro=(a2, b2, True), db=c2.bias.grad)
-                if not isinstance(sk, Identity):
+                if not isinstance(sk, Identity) and not skip_fused:
                     ops.wgrad(x0.t, dy, sk.conv.weight.grad, src1=x1.t if x1 else None, ks=1, pad=0,
                               db=sk.conv.bias.grad)
             self._wg(wg2, N * HW)
@@ -771,6 +776,10 @@ class UNetEngine:
             d1, acc1 = _gdest(x1)
             if isinstance(sk, Identity):
                 ops.gn_bwd_apply(dz1, x0.t, x1.t if x1 else None, P1, Q1, R1, extra, d0, acc0, d1, acc1)
+            elif skip_fused:
+                if not ops.skip_bwd(dy, self.wc.get(sk.conv.weight, 1), dz1, x0.t, x1.t if x1 else None, P1, Q1, R1,
+                                    d0, acc0, d1, acc1, sk.conv.weight.grad, sk.conv.bias.grad):
+                    raise RuntimeError("skip_bwd: the plan that took this block at trace time now refuses it")
             else:
                 ops.conv1x1_gn_apply(dy, self.wc.get(sk.conv.weight, 1), dz1, x0.t, x1.t if x1 else None,
                                      P1, Q1, R1, d0, acc0, d1, acc1)

@@ -14,7 +14,7 @@ import torch
 
 from .. import _lib
 from . import tuning, wgrad_plan
-from .._lib import ConvDesc, GnApplyDesc, GnOutDesc, WgradDesc
+from .._lib import ConvDesc, GnApplyDesc, GnOutDesc, SkipBwdDesc, SkipBwdPlan, WgradDesc
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -1008,6 +1008,70 @@ def wgrad(src0, dy, dw, *, src1=None, ks=3, stride=1, pad=1, upsample=False, pro
     job.d.splits = job.single_splits() if splits is None else splits
     ws = _wgrad_workspace([job])   # noqa: F841
     _lib.call("fmd_wgrad", C.byref(job.d), stream())
+
+
+# the skip conv's weight / bias gradient inside the GroupNorm-1 backward apply pass (fmd_skip_bwd); SKIP_BWD=0
+# (runtime/tuning.py): fmd_conv_gn_apply + the ks=1 weight gradient (A/B runs, bisection)
+SKIP_BWD = bool(tuning.get("SKIP_BWD"))
+SKIP_BWD_MIN_TILES = tuning.get("SKIP_BWD_MIN_TILES")   # fewest pixel tiles per group the plan takes (measured floor)
+
+
+class _SkipWs:
+    """What ``_wgrad_workspace`` sizes: the fused launch's slabs are those of a 1x1 weight gradient with
+    ``slabs`` splits."""
+    __slots__ = ("d", "device")
+
+    def __init__(self, Kd, C0, C1, slabs, device):
+        self.d = WgradDesc()
+        self.d.K, self.d.C0, self.d.C1, self.d.ks, self.d.splits = Kd, C0, C1, 1, slabs
+        self.device = device
+
+
+def _skip_bwd_desc(N, HW, C0, C1, Kd, groups=0, min_tiles=None) -> SkipBwdDesc:
+    d = SkipBwdDesc()
+    d.N, d.HW, d.C0, d.C1, d.Kd, d.groups, d.num_cu = N, HW, C0, C1, Kd, groups, NUM_CU
+    d.min_tiles = SKIP_BWD_MIN_TILES if min_tiles is None else min_tiles
+    return d
+
+
+def skip_bwd_plan(N, HW, C0, C1, Kd, groups=0, min_tiles=None) -> Optional[SkipBwdPlan]:
+    """fmd_skip_bwd_plan's answer for a skip conv of Kd output channels over N x HW pixels of a C0|C1 input
+    (host arithmetic only): the plan, or None where the fused pass is not taken (or SKIP_BWD=0).  ``min_tiles``: the
+    floor on pixel tiles per group (default SKIP_BWD_MIN_TILES; tests pass 0 to run small shapes)."""
+    if not SKIP_BWD:
+        return None
+    p = SkipBwdPlan()
+    rc = _lib.lib().fmd_skip_bwd_plan(C.byref(_skip_bwd_desc(N, HW, C0, C1, Kd, groups, min_tiles)), C.byref(p))
+    return p if rc == 0 and p.taken else None
+
+
+def skip_bwd(dy, wgt_t, dz, x0, x1, P, Q, R, dx0, acc0, dx1, acc1, dw, db, accumulate=True, groups=0,
+             min_tiles=None) -> bool:
+    """The skip conv's whole backward in one pass (fmd_skip_bwd): dx as ``conv1x1_gn_apply`` (same arguments,
+    bit-identical) and dw / db (+)= the ks=1 weight gradient of ``wgrad(x0, dy, dw, src1=x1, ks=1, pad=0, db=db)``.
+    ``groups``: forced pixel groups, ``min_tiles``: the plan's floor (tests).  Returns False, with nothing launched,
+    where the plan refuses."""
+    _need_cuda(dy, "skip_bwd")
+    N, Kd = dy.shape[0], dy.shape[-1]
+    HW = dy[0, ..., 0].numel()
+    C0 = x0.shape[-1]
+    C1 = x1.shape[-1] if x1 is not None else 0
+    plan = skip_bwd_plan(N, HW, C0, C1, Kd, groups, min_tiles)
+    if plan is None:
+        return False
+    d = _skip_bwd_desc(N, HW, C0, C1, Kd, groups, min_tiles)
+    d.dy, d.wgt_t = _p(dy), _p(wgt_t)
+    d.g.dz, d.g.x0, d.g.x1, d.g.C0 = _p(dz), _p(x0), _p(x1), C0
+    d.g.P, d.g.Q, d.g.R = _p(P), _p(Q), _p(R)
+    d.g.dx0, d.g.acc0, d.g.dx1, d.g.acc1 = _p(dx0), int(acc0), _p(dx1), int(acc1)
+    d.dw, d.db, d.accumulate = _p(dw), _p(db), int(accumulate)
+    job = _SkipWs(Kd, C0, C1, plan.slabs, dy.device)
+    ws = _wgrad_workspace([job])   # noqa: F841 -- stream-ordered allocation
+    if ws.numel() < plan.ws_floats:
+        raise RuntimeError("skip_bwd: workspace smaller than the plan's")
+    d.ws = job.d.ws
+    _lib.call("fmd_skip_bwd", C.byref(d), stream())
+    return True
 
 
 def prep_weights(w: torch.Tensor, mode: int, Kpad: Optional[int] = None, Cpad: Optional[int] = None, out=None):

@@ -63,6 +63,10 @@ TABLE = {
                                     "the 128^2 level and below); larger levels run each weight gradient at once, "
                                     "its operands still in the Infinity Cache (DESIGN.md round 7: the 256^2 level "
                                     "measured no gain grouped)"),
+    "SKIP_BWD": (1, "ResBlock skip conv: weight, bias and data gradient in the GroupNorm-1 backward pass "
+                    "(fmd_skip_bwd) where its plan takes the block (0: fmd_conv_gn_apply + the ks=1 weight gradient)"),
+    "SKIP_BWD_MIN_TILES": (8, "... only with at least this many 64-pixel tiles per pixel group (config B at batch 8: "
+                              "the 128^2 level and above, the levels traced faster fused; DESIGN.md round 17)"),
     "WGRAD_GROUP_SPLITS": (0, "grouped weight gradients: 0 = the group plan's splits, 1 = every job's own ungrouped "
                               "splits (bit-identical to WGRAD_GROUP=0; parity bisection)"),
 }

@@ -348,6 +348,40 @@ int64_t fmd_wgrad_workspace(const fmd_wgrad_desc* d);
 int fmd_wgrad_group(const fmd_wgrad_desc* descs, int32_t n, fmd_stream_t s);
 /* The halo launch of a group alone (partial slabs only, no reduce); 1 when no job qualifies. */
 int fmd_wgrad_halo_group(const fmd_wgrad_desc* descs, int32_t n, fmd_stream_t s);
+/* The combine of fmd_wgrad alone: dw / db (+)= the sum of the d->splits partial slabs in d->ws (layout of
+ * fmd_wgrad_workspace), for producers that write the slabs themselves (fmd_skip_bwd). */
+int fmd_wgrad_combine(const fmd_wgrad_desc* d, fmd_stream_t s);
+
+/* The whole backward of the ResBlock's 1x1 skip conv in one pass over dy and the block input (csrc/skip_bwd.hip):
+ * dx = round_bf16(dy . W_s^T) + P*dz + Q*x + R (+ dx) exactly as fmd_conv_gn_apply (bit-identical), and
+ * dW_s[Kd][C] (+)= dy^T . x, db_s[Kd] (+)= sum_p dy from the same staged tiles (persistent workgroups, fp32 partial
+ * slabs, one fmd_wgrad_combine).  Replaces fmd_conv_gn_apply + the ks = 1 fmd_wgrad of the same block
+ * (autograd of the skip nn.Conv2d, src/nn/blocks/residual.py:77-82,120). */
+typedef struct fmd_skip_bwd_desc {
+  int32_t N, HW;            /* images, pixels per image (any spatial rank): M = N * HW */
+  int32_t C0, C1, Kd;       /* concat sources of the block input; skip-conv output channels */
+  const void* dy;           /* bf16 [M][Kd] */
+  const void* wgt_t;        /* bf16 [C0 + C1][Kd]: mode-1 (data-gradient) weights */
+  fmd_gn_apply_desc g;      /* as for fmd_conv_gn_apply; g.C0 == C0 */
+  float* dw;                /* fp32 [Kd][C0 + C1] (reference layout, 1x1) */
+  float* db;                /* fp32 [Kd] or NULL */
+  int32_t accumulate;
+  float* ws;                /* fp32 workspace, plan.ws_floats */
+  int32_t groups;           /* 0: the plan's pixel groups; > 0: forced (tests) */
+  int32_t num_cu;           /* compute units of the device (0: 256) */
+  int32_t min_tiles;        /* the plan's own groups: taken only with at least this many 64-pixel tiles per group */
+} fmd_skip_bwd_desc;
+typedef struct fmd_skip_bwd_plan_t {
+  int32_t taken;            /* 0: not taken -- run fmd_conv_gn_apply + fmd_wgrad */
+  int32_t c_tile;           /* input channels per workgroup */
+  int32_t workgroups;       /* pixel groups x c-tiles launched */
+  int32_t slabs;            /* partial slabs written: min(pixel groups, pixel tiles) */
+  int64_t ws_floats;        /* slabs * (Kd * C + Kd): exactly what the launch writes */
+} fmd_skip_bwd_plan_t;
+/* Host arithmetic only (reads the descriptor's scalars).  Returns 0 (taken) or 1 (not taken). */
+int fmd_skip_bwd_plan(const fmd_skip_bwd_desc* d, fmd_skip_bwd_plan_t* out);
+/* -1: the plan refuses the descriptor (nothing launched). */
+int fmd_skip_bwd(const fmd_skip_bwd_desc* d, fmd_stream_t s);
 
 /* ------------------------------------------------------------- groupnorm
  * nn.GroupNorm (src/nn/ops/normalization.py:11-19, attention.py:97) is never
