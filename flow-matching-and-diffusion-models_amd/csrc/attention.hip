@@ -183,8 +183,8 @@ __global__ __launch_bounds__(256) void la_ctx_part(const bf16r* __restrict__ kvs
     la_combine_stats(a.nchk, wstat + (size_t)bh * a.nchk * 2 * LA_D, m, z);
     M[t] = m;
     Zi[t] = z > 0.f ? 1.f / z : 0.f;
-    if (c == 0) {
-      state[(size_t)bh * LA_STATE + LA_D * LA_D + t] = m;
+    if (c == 0) {   // columns >= dh have no rows (m = -inf): the saved state stays finite
+      state[(size_t)bh * LA_STATE + LA_D * LA_D + t] = m > -INFINITY ? m : 0.f;
       state[(size_t)bh * LA_STATE + LA_D * LA_D + LA_D + t] = z;
     }
   }
