@@ -341,35 +341,49 @@ def _check_conv(c: Conv, ks, stride, pad):
         raise NotImplementedError(f"unexpected conv geometry {c.kernel_size}/{c.stride}/{c.padding}")
 
 
-class UNetEngine:
-    def __init__(self, model):
-        from ..models.unet.unet import EfficientUNetND
-        from ..models.unet.unet_diffusers_nd import UNetDiffusersND
+def route3x3(N, sp, K, Cin, *, stride=1, upsample=False, transposed=False, pro=False, exact_weight=True, ks=3) -> str:
+    """Kernel a 3x3 (3x3x3) pad-1 gather runs on: "halo", "s2d", "d2s" or "igemm" (the implicit GEMM).
+
+    ``sp`` is the fine grid, (H, W) or (D, H, W): the input of a forward gather (before its nearest-x2
+    ``upsample``), the output of a ``transposed`` one.  The gather reads ``Cin`` channels and writes ``K``; a data
+    gradient is the gather from dy, so its ``Cin`` is dy's channel count.  ``pro``: a GroupNorm prologue is fused
+    into the gather.  ``exact_weight``: the operand channels are the master weight's own (no channel padding),
+    which the stride-2 tilings (WeightCache.s2d) assume.  ``ks=4``: the data gradient of a conv on a nearest-x2
+    input, a 4x4 (4x4x4) stride-2 gather from the upsampled grid ``sp``.  Reads the DEPTH_HALO / S2D_HALO /
+    S2D_3D switches at call time; ints and bools only, no library call."""
+    d3 = len(sp) == 3
+    D, H, W = sp if d3 else (0, *sp)
+    if stride == 1:
+        f = 2 if upsample else 1   # 3-D: the depth-tap halo, one image per output depth slice
+        on = not transposed and (DEPTH_HALO or not d3)
+        return "halo" if on and ops.halo_eligible(N * f * D if d3 else N, H, f * H, f * W, K, upsample=upsample,
+                                                  Cin=Cin, pro=pro, ztaps=3 if d3 else 1) else "igemm"
+    # S2D_3D implies S2D_HALO as the module sets them; set on its own it still switches the 4x4x4 gather
+    on = (S2D_3D and (S2D_HALO or ks == 4)) if d3 else S2D_HALO
+    if not (on and stride == 2 and exact_weight and not pro):
+        return "igemm"
+    h, w = H // 2, W // 2               # the coarse grid; an odd fine size fails either predicate
+    dd = (D, D // 2) if d3 else ()
+    if transposed:
+        return "d2s" if ks == 3 and ops.d2s_eligible(N, h, w, H, W, K, Cin, *dd[::-1]) else "igemm"
+    return "s2d" if ops.s2d_eligible(N, H, W, h, w, K, Cin, ks, *dd) else "igemm"
+
+
+class LayerEngine:
+    """The fused layers over one module tree: weight cache, weight-gradient queue and the layer methods.  The
+    walkers (UNetEngine, VAEEngine, the one-block engine of runtime/standalone.py) decide the order of the
+    layers; everything a layer method reads from ``self`` is set here."""
+
+    def __init__(self, model, dims1: Optional[bool] = None):
         self._model = weakref.ref(model)
-        if isinstance(model, EfficientUNetND):
-            self.kind = "efficient"
-        elif isinstance(model, UNetDiffusersND):
-            self.kind = "diffusers"
-        else:
-            raise TypeError(type(model))
         self.wc = WeightCache()
-        self._tt = None   # precomputed per-step time embeddings (set_time_table)
-        self.gl, self.gl_slot = self._group_emb_layers(model)
+        self._wq = ops.WgradQueue()   # weight gradients waiting for their level's grouped launch (_wg / _join)
+        self._head_bwd = None         # backward of the output head, set by head() / unpool_layer() under a tape
+        self._drop_state = None       # (device seed counter, per-block salts), made by the first dropout block
+        self.gl, self.gl_slot = None, {}   # grouped ResBlock emb projections (UNetEngine)
         # spatial_dims = 1: signals run as (L, 1) images -- 1-D k-tap weights embedded as k x k
         # (WeightCache.embed1d), resampling along the first dim only
-        self.dims1 = next(c for c in model.modules() if isinstance(c, Conv)).dims == 1
-        self._wq = ops.WgradQueue()   # weight gradients waiting for their level's grouped launch (_wg / _join)
-
-    @staticmethod
-    def _group_emb_layers(model):
-        """ResBlocks whose emb projection feeds the block (scale-shift or added embedding) share one
-        grouped launch; a mixed emb_activation_before_proj keeps the per-block path."""
-        blocks = [mod for mod in model.modules() if isinstance(mod, ResBlockND)
-                  and (mod.use_scale_shift_norm or mod.add_embedding_to_hidden)]
-        if not blocks or len({bool(b.emb_activation_before_proj) for b in blocks}) != 1:
-            return None, {}
-        gl = ops.GroupedLinear([b.emb_layers for b in blocks], blocks[0].emb_activation_before_proj)
-        return gl, {id(b): (gl.off[i], gl.O[i]) for i, b in enumerate(blocks)}
+        self.dims1 = (next(c for c in model.modules() if isinstance(c, Conv)).dims == 1) if dims1 is None else dims1
 
     @property
     def m(self):
@@ -392,53 +406,30 @@ class UNetEngine:
                 out, st = ops.conv_small(x.t, conv.out_channels, self.wc.get(conv.weight, 0), mode=mode,
                                          bias=conv.bias)
                 return Act(out, st)
-        Ho_ = ops.out_hw(sp[0], 3, stride, 1, upsample)
-        if len(sp) == 2:
-            halo = stride == 1 and ops.halo_eligible(N_, sp[0], Ho_, ops.out_hw(sp[1], 3, stride, 1, upsample),
-                                                     conv.out_channels, upsample=upsample, Cin=Cin)
-        else:   # depth-tap halo, nearest-x2 included (output depth 2D)
-            Do_ = 2 * sp[0] if upsample else sp[0]
-            halo = DEPTH_HALO and stride == 1 and ops.halo_eligible(
-                N_ * Do_, sp[1], ops.out_hw(sp[1], 3, 1, 1, upsample), ops.out_hw(sp[2], 3, 1, 1, upsample),
-                conv.out_channels, upsample=upsample, Cin=Cin, ztaps=3)
-        s2d = S2D_HALO and stride == 2 and conv.weight.shape[1] == Cin and (
-            ops.s2d_eligible(N_, sp[0], sp[1], sp[0] // 2, sp[1] // 2, conv.out_channels, Cin, 3) if len(sp) == 2
-            else S2D_3D and ops.s2d_eligible(N_, sp[1], sp[2], sp[1] // 2, sp[2] // 2, conv.out_channels, Cin, 3,
-                                             sp[0], sp[0] // 2))
-        if s2d:   # DownsampleND's conv on the space-to-depth halo kernel (3-D: depth taps as chunks)
+        exact = conv.weight.shape[1] == Cin
+        route = route3x3(N_, sp, conv.out_channels, Cin, stride=stride, upsample=upsample, exact_weight=exact)
+        if route == "s2d":   # DownsampleND's conv on the space-to-depth halo kernel (3-D: depth taps as chunks)
             out, st = ops.conv(x.t, conv.out_channels, None, ks=3, stride=2, pad=1, bias=conv.bias, want_stats="free",
                                s2d_tiled=self.wc.s2d(conv.weight, 0))
-        else:
-            w, wt = self._wts(conv.weight, 0, halo, None, Cin)
+        else:   # the depth-tap halo takes the nearest-x2 too (output depth 2D)
+            w, wt = self._wts(conv.weight, 0, route == "halo", None, Cin)
             out, st = ops.conv(x.t, conv.out_channels, w, ks=3, stride=stride, pad=1, upsample=upsample,
                                bias=conv.bias, want_stats="free", wgt_tiled=wt)
         o = Act(out, st)
         if ctx.tape is not None:
             def bwd():
                 dy = o.grad
-
-                def wg():
-                    tgt = self._wgrad_target(conv, Cin)
-                    ops.wgrad(x.t, dy, tgt, ks=3, stride=stride, pad=1, upsample=upsample,
-                              db=conv.bias.grad if conv.bias is not None else None,
-                              immediate=tgt is not conv.weight.grad)
-                    self._wgrad_finish(conv, Cin, tgt)
-                self._wg(wg, dy.numel() // dy.shape[-1])
+                self._wg(lambda: self._wgrad_padded(conv, x.t, dy, Cin, ks=3, stride=stride, pad=1,
+                                                    upsample=upsample), dy.numel() // dy.shape[-1])
                 if not x.need_grad:
                     return
                 g, acc = _gdest(x)
                 # the tiled mode-1 weight covers exactly conv.weight.shape[0] gradient channels: a channel-padded dy
                 # would read past it, so such a dy takes the generic path
-                if upsample and len(sp) == 2 and S2D_HALO and conv.weight.shape[1] == Cin and \
-                        dy.shape[-1] == conv.weight.shape[0] and ops.s2d_eligible(
-                        N_, 2 * sp[0], 2 * sp[1], sp[0], sp[1], Cin, dy.shape[-1], 4):
-                    # nearest-x2 folded into a 4x4 stride-2 gather, on the space-to-depth halo kernel
-                    ops.conv(dy, Cin, None, ks=4, stride=2, pad=1, out_hw_=sp, out=g, accumulate=bool(acc),
-                             s2d_tiled=self.wc.s2d(conv.weight, 1))
-                elif upsample and len(sp) == 3 and S2D_3D and conv.weight.shape[1] == Cin and \
-                        dy.shape[-1] == conv.weight.shape[0] and ops.s2d_eligible(
-                        N_, 2 * sp[1], 2 * sp[2], sp[1], sp[2], Cin, dy.shape[-1], 4, 2 * sp[0], sp[0]):
-                    # 3-D: the nearest-x2 copy folded into a 4x4x4 stride-2 gather (the depth taps as chunks)
+                if upsample and route3x3(N_, tuple(2 * v for v in sp), Cin, dy.shape[-1], stride=2, ks=4,
+                                         exact_weight=exact and dy.shape[-1] == conv.weight.shape[0]) == "s2d":
+                    # nearest-x2 folded into a 4x4 (4x4x4: the depth taps as chunks) stride-2 gather, on the
+                    # space-to-depth halo kernel
                     ops.conv(dy, Cin, None, ks=4, stride=2, pad=1, out_hw_=sp, out=g, accumulate=bool(acc),
                              s2d_tiled=self.wc.s2d(conv.weight, 1))
                 elif upsample and len(sp) == 2:
@@ -469,13 +460,7 @@ class UNetEngine:
         o = Act(out)
         if ctx.tape is not None:
             def bwd():
-                def wg():
-                    tgt = self._wgrad_target(conv, Cin)
-                    ops.wgrad(x.t, o.grad, tgt, ks=pf, stride=pf, pad=0,
-                              db=conv.bias.grad if conv.bias is not None else None,
-                              immediate=tgt is not conv.weight.grad)
-                    self._wgrad_finish(conv, Cin, tgt)
-                self._wg(wg)
+                self._wg(lambda: self._wgrad_padded(conv, x.t, o.grad, Cin, ks=pf, stride=pf, pad=0))
             ctx.tape.append(bwd)
         return o
 
@@ -565,41 +550,30 @@ class UNetEngine:
         Stride 1 = forward gather with flipped taps (so a 2-D one runs on the halo-tiled kernel);
         stride 2 = transposed gather."""
         sp = tuple(sp)
+        route = route3x3(dy.shape[0], sp, Cin, dy.shape[-1], stride=stride, transposed=stride != 1,
+                         pro=bool(kw.get("pro")),
+                         exact_weight=Kpad is None and w.shape[1] == Cin and w.dim() == len(sp) + 2)
         if stride == 1:
-            halo = self._halo_ok(dy.shape[0], sp, Cin, dy.shape[-1])
-            base, tiled = self._wts(w, 3, halo, Kpad, None)
+            base, tiled = self._wts(w, 3, route == "halo", Kpad, None)
             return ops.conv(dy, Cin, base, ks=3, stride=1, pad=1, out_hw_=sp, wgt_tiled=tiled, **kw)
-        if S2D_HALO and Kpad is None and w.shape[1] == Cin and not kw.get("pro") and (
-                ops.d2s_eligible(dy.shape[0], dy.shape[1], dy.shape[2], sp[0], sp[1], Cin, dy.shape[-1])
-                if len(sp) == 2 and w.dim() == 4 else
-                S2D_3D and len(sp) == 3 and w.dim() == 5 and ops.d2s_eligible(dy.shape[0], dy.shape[2], dy.shape[3], sp[1], sp[2],
-                                                                    Cin, dy.shape[-1], dy.shape[1], sp[0])):
+        if route == "d2s":
             # transposed stride-2 gather onto the depth-to-space view, on the halo kernel (3-D: 8 classes)
             return ops.conv(dy, Cin, None, ks=3, stride=2, pad=1, transposed=True, out_hw_=sp,
                             s2d_tiled=self.wc.s2d(w, 2), **kw)
         return ops.conv(dy, Cin, self.wc.get(w, 1, Kpad, None), ks=3, stride=stride, pad=1, transposed=True,
                         out_hw_=sp, **kw)
 
-    @staticmethod
-    def _halo_ok(N, sp, K, Cin, pro=False) -> bool:
-        """3x3 (3x3x3) stride-1 conv onto the grid ``sp`` on the halo kernel (3-D: depth-tap chunks)."""
-        if len(sp) == 2:
-            return ops.halo_eligible(N, sp[0], sp[0], sp[1], K, Cin=Cin, pro=pro)
-        D, H, W = sp
-        return DEPTH_HALO and ops.halo_eligible(N * D, H, H, W, K, Cin=Cin, pro=pro, ztaps=3)
-
-    def _wgrad_target(self, conv: Conv, Cin: int):
-        """fp32 buffer the wgrad kernel writes: param.grad itself unless channels were padded."""
-        if conv.weight.shape[1] == Cin and conv.weight.shape[0] % 8 == 0:
-            return conv.weight.grad
-        return torch.zeros((max(8, -(-conv.weight.shape[0] // 8) * 8), Cin, *conv.weight.shape[2:]),
-                           device=conv.weight.device, dtype=F32)
-
-    def _wgrad_finish(self, conv: Conv, Cin: int, tgt):
-        if tgt is conv.weight.grad:
-            return
-        K, C = conv.weight.shape[:2]
-        conv.weight.grad.add_(tgt[:K, :C])
+    def _wgrad_padded(self, conv: Conv, x, dy, Cin: int, **geom):
+        """Weight and bias gradient of ``conv`` over an input of ``Cin`` channels: into param.grad itself
+        unless channels were padded; then through a zeroed fp32 temporary that is cut to size and added."""
+        w = conv.weight
+        padded = w.shape[1] != Cin or w.shape[0] % 8 != 0
+        tgt = w.grad
+        if padded:
+            tgt = torch.zeros((max(8, -(-w.shape[0] // 8) * 8), Cin, *w.shape[2:]), device=w.device, dtype=F32)
+        ops.wgrad(x, dy, tgt, db=conv.bias.grad if conv.bias is not None else None, immediate=padded, **geom)
+        if padded:
+            w.grad.add_(tgt[:w.shape[0], :w.shape[1]])
 
     def res_block(self, m: ResBlockND, xs: List[Act], ctx: Ctx):
         x0 = xs[0]
@@ -633,10 +607,10 @@ class UNetEngine:
             o = self._res_block_small(m, x0, x1, eo, es, ss, add)
             if o is not None:
                 return o
-        halo1 = self._halo_ok(N, sp, Cout, Cin, pro=True)
+        halo1 = route3x3(N, sp, Cout, Cin, pro=True) == "halo"
         mat1 = _materialise(halo1, x1, Cin, HW, len(sp) == 3)
         if mat1 and not halo1:   # without the fused prologue the halo kernel's affine-table limit is moot
-            halo1 = self._halo_ok(N, sp, Cout, Cin)
+            halo1 = route3x3(N, sp, Cout, Cin) == "halo"
         # a 1x1 level (the bottom of a small latent UNet): the 3x3 convs are their centre taps (exact)
         point = POINT_1X1 and sp == (1, 1) and c1.weight.dim() == 4 and not halo1
         pk = dict(ks=1, pad=0) if point else {}
@@ -654,7 +628,7 @@ class UNetEngine:
             t1 = ops.gn_apply_fwd(x0.t, x1.t if x1 else None, a1, b1) if mat1 else None
         pf1 = (dict(st0=_stats(x0), st1=_stats(x1), groups=g1.num_groups, eps=g1.eps, gamma=g1.weight, beta=g1.bias)
                if a1 is None and t1 is None else None)
-        halo2 = self._halo_ok(N, sp, Cout, Cout, pro=True)
+        halo2 = route3x3(N, sp, Cout, Cout, pro=True) == "halo"
         mat2 = _materialise(halo2, None, Cout, HW, len(sp) == 3) or bool(drop)   # dropout acts on the materialised operand
         fuse2 = mat2 and ops.gn_fused_eligible(HW, Cout, Cout, g2.num_groups)
         src1 = x1.t if (x1 is not None and t1 is None) else None
@@ -663,9 +637,9 @@ class UNetEngine:
                if keep_g and t1 is None and halo1 and not point and Cin % HALO_BK == 0 else None)
         # small level, split-K conv1: GroupNorm-2 (+ scale/shift) + SiLU inside conv1's combine (fmd_conv_gn);
         # not with the additive embedding under a tape (its backward needs conv1's statistics slab)
-        gnreq = (dict(groups=g2.num_groups, eps=g2.eps, gamma=g2.weight, beta=g2.bias, emb=eo if ss else None,
-                      emb_stride=es if ss else 0, emb_mode=1 if ss else 0)
-                 if fuse2 and not (add and ctx.tape is not None) else None)
+        emb2 = dict(emb=eo, emb_stride=es, emb_mode=1) if ss else dict(emb=None, emb_stride=0, emb_mode=0)
+        gn2 = dict(groups=g2.num_groups, eps=g2.eps, gamma=g2.weight, beta=g2.bias, **emb2)
+        gnreq = dict(gn2) if fuse2 and not (add and ctx.tape is not None) else None
         h, hst = ops.conv(t1 if t1 is not None else x0.t, Cout, w1, src1=src1,
                           pro=None if (t1 is not None or pf1 is not None) else (a1, b1, True), pro_fold=pf1,
                           bias=c1.bias, bias_nc=eo.contiguous() if add else None,
@@ -675,18 +649,12 @@ class UNetEngine:
         if fuse2 and gnreq is not None and "res" in gnreq:
             a2, b2, mr2, t2 = gnreq["res"]
         elif fuse2:
-            a2, b2, mr2, t2 = ops.gn_fused_apply(h, None, g2.num_groups, g2.eps, g2.weight, g2.bias,
-                                                 emb=eo if ss else None, emb_stride=es if ss else 0,
-                                                 emb_mode=1 if ss else 0)
+            a2, b2, mr2, t2 = ops.gn_fused_apply(h, None, g2.num_groups, g2.eps, g2.weight, g2.bias, **emb2)
         elif ctx.tape is None and not mat2 and halo2 and len(sp) == 2 and hst is not None and ops.HALO_FOLD:
             a2 = b2 = mr2 = None   # forward only, halo conv2: GroupNorm-2 folded inside the conv (as conv1)
-        elif ss:
-            a2, b2, mr2 = ops.gn_prep(hst, None, N, HW, Cout, 0, g2.num_groups, g2.eps, g2.weight, g2.bias, emb=eo,
-                                      emb_stride=es, emb_mode=1)
         else:
-            a2, b2, mr2 = ops.gn_prep(hst, None, N, HW, Cout, 0, g2.num_groups, g2.eps, g2.weight, g2.bias)
-        pf2 = (dict(st0=hst, groups=g2.num_groups, eps=g2.eps, gamma=g2.weight, beta=g2.bias, emb=eo if ss else None,
-                    emb_stride=es if ss else 0) if a2 is None and t2 is None else None)
+            a2, b2, mr2 = ops.gn_prep(hst, None, N, HW, Cout, 0, g2.num_groups, g2.eps, g2.weight, g2.bias, **emb2)
+        pf2 = dict(gn2, st0=hst) if a2 is None and t2 is None else None
         sk = m.skip_connection
         kw = {}
         if isinstance(sk, Identity):
@@ -696,7 +664,7 @@ class UNetEngine:
         else:
             _check_conv(sk.conv, 1, 1, 0)
         if mat2 and not halo2:
-            halo2 = self._halo_ok(N, sp, Cout, Cout)
+            halo2 = route3x3(N, sp, Cout, Cout) == "halo"
         if not isinstance(sk, Identity):
             s2, s2t = self._wts(sk.conv.weight, 0, halo2)
             kw.update(src2=x0.t, src3=x1.t if x1 else None, wgt2=s2, wgt2_tiled=s2t, bias2=sk.conv.bias)
@@ -750,15 +718,13 @@ class UNetEngine:
             else:
                 demb, ds_ = None, 0
             if ss:
-                P2, Q2, R2 = ops.gn_bwd_prep(s2, N, HW, Cout, g2.num_groups, mr2, g2.weight, g2.bias, g2.weight.grad,
-                                             g2.bias.grad, emb=eo, emb_stride=es, emb_mode=1, demb=demb,
-                                             demb_stride=ds_)
-            elif add:
-                P2, Q2, R2 = ops.gn_bwd_prep(s2, N, HW, Cout, g2.num_groups, mr2, g2.weight, g2.bias, g2.weight.grad,
-                                             g2.bias.grad, emb_mode=2, demb=demb, demb_stride=ds_, fwd=hst)
+                dk = dict(emb2, demb=demb, demb_stride=ds_)
+            elif add:   # the additive embedding's gradient reads conv1's statistics slab
+                dk = dict(emb_mode=2, demb=demb, demb_stride=ds_, fwd=hst)
             else:
-                P2, Q2, R2 = ops.gn_bwd_prep(s2, N, HW, Cout, g2.num_groups, mr2, g2.weight, g2.bias, g2.weight.grad,
-                                             g2.bias.grad)
+                dk = {}
+            P2, Q2, R2 = ops.gn_bwd_prep(s2, N, HW, Cout, g2.num_groups, mr2, g2.weight, g2.bias, g2.weight.grad,
+                                         g2.bias.grad, **dk)
             dh = torch.empty_like(h)
             ops.gn_bwd_apply(dz2, h, None, P2, Q2, R2, None, dh, 0)
             del dz2
@@ -842,7 +808,7 @@ class UNetEngine:
         """(device seed counter, per-block salt) for ResBlockND dropout; the counter advances once per forward
         (a device-side add, so every replay of a captured step draws fresh masks) and the backward reuses the
         forward's value to regenerate its masks."""
-        st = getattr(self, "_drop_state", None)
+        st = self._drop_state
         if st is None:
             # the counter starts from torch's (host) generator, so training.seed / set_seed selects the mask
             # sequence, and is offset by the data-parallel rank so ranks draw different masks for the same local
@@ -1072,6 +1038,55 @@ class UNetEngine:
             self._head_bwd = bwd
         return out
 
+    def _apply(self, layer, h: Act, ctx: Ctx) -> Act:
+        if isinstance(layer, ResBlockND):
+            return self.res_block(layer, [h], ctx)
+        if isinstance(layer, ConvND):
+            return self.conv_layer(layer.conv, h, ctx)
+        if isinstance(layer, DownsampleND):
+            if not layer.use_conv:
+                return self.resample_layer(h, ctx, up=False)
+            return self.conv_layer(layer.op.conv, h, ctx, stride=2)
+        if isinstance(layer, UpsampleND):
+            if not layer.use_conv:
+                return self.resample_layer(h, ctx, up=True)
+            if self.dims1:   # nearest-x2 along the signal only, then the 3-tap conv
+                return self.conv_layer(layer.conv.conv, self.resample_layer(h, ctx, up=True), ctx)
+            return self.conv_layer(layer.conv.conv, h, ctx, upsample=True)
+        if isinstance(layer, (SpatialSelfAttention, DiffusersAttentionND)):
+            return self.attention(layer, h, ctx)
+        if isinstance(layer, SpatialCrossAttention):
+            return self.cross_attention(layer, h, ctx)
+        raise NotImplementedError(type(layer).__name__)
+
+
+class UNetEngine(LayerEngine):
+    """The UNet walker: time MLP, forward over the reference's module order, the segmented backward."""
+
+    def __init__(self, model):
+        from ..models.unet.unet import EfficientUNetND
+        from ..models.unet.unet_diffusers_nd import UNetDiffusersND
+        if isinstance(model, EfficientUNetND):
+            self.kind = "efficient"
+        elif isinstance(model, UNetDiffusersND):
+            self.kind = "diffusers"
+        else:
+            raise TypeError(type(model))
+        super().__init__(model)
+        self._tt = None   # precomputed per-step time embeddings (set_time_table)
+        self.gl, self.gl_slot = self._group_emb_layers(model)
+
+    @staticmethod
+    def _group_emb_layers(model):
+        """ResBlocks whose emb projection feeds the block (scale-shift or added embedding) share one
+        grouped launch; a mixed emb_activation_before_proj keeps the per-block path."""
+        blocks = [mod for mod in model.modules() if isinstance(mod, ResBlockND)
+                  and (mod.use_scale_shift_norm or mod.add_embedding_to_hidden)]
+        if not blocks or len({bool(b.emb_activation_before_proj) for b in blocks}) != 1:
+            return None, {}
+        gl = ops.GroupedLinear([b.emb_layers for b in blocks], blocks[0].emb_activation_before_proj)
+        return gl, {id(b): (gl.off[i], gl.O[i]) for i, b in enumerate(blocks)}
+
     def set_time_table(self, t_steps: Optional[torch.Tensor], N: int = 0, index: Optional[torch.Tensor] = None):
         """Precompute the time embedding (+ grouped ResBlock projections) of every step of a fixed sampling
         schedule ``t_steps`` [S] (each for a batch of N); forward(save=False) then copies row ``index[0]``
@@ -1101,7 +1116,7 @@ class UNetEngine:
 
     def time_mlp(self, t, ctx_save, N, t_scale=1.0, t_trunc=False):
         m = self.m
-        tt = getattr(self, "_tt", None)
+        tt = self._tt
         if tt is not None and not ctx_save and N == tt["N"] and t_scale == 1.0 and not t_trunc:
             emb = torch.empty((N, tt["emb_cols"]), device=tt["emb"].device, dtype=tt["emb"].dtype)
             ops.gather_row(tt["emb"], tt["index"], emb)
@@ -1214,27 +1229,6 @@ class UNetEngine:
                     h = self._apply(blk.upsamplers[0], h, ctx)
             out = self.head(m.conv_norm_out, m.conv_out, h, ctx)
         return out, ctx
-
-    def _apply(self, layer, h: Act, ctx: Ctx) -> Act:
-        if isinstance(layer, ResBlockND):
-            return self.res_block(layer, [h], ctx)
-        if isinstance(layer, ConvND):
-            return self.conv_layer(layer.conv, h, ctx)
-        if isinstance(layer, DownsampleND):
-            if not layer.use_conv:
-                return self.resample_layer(h, ctx, up=False)
-            return self.conv_layer(layer.op.conv, h, ctx, stride=2)
-        if isinstance(layer, UpsampleND):
-            if not layer.use_conv:
-                return self.resample_layer(h, ctx, up=True)
-            if self.dims1:   # nearest-x2 along the signal only, then the 3-tap conv
-                return self.conv_layer(layer.conv.conv, self.resample_layer(h, ctx, up=True), ctx)
-            return self.conv_layer(layer.conv.conv, h, ctx, upsample=True)
-        if isinstance(layer, (SpatialSelfAttention, DiffusersAttentionND)):
-            return self.attention(layer, h, ctx)
-        if isinstance(layer, SpatialCrossAttention):
-            return self.cross_attention(layer, h, ctx)
-        raise NotImplementedError(type(layer).__name__)
 
     # Backward segments, in backward order: 0 = output head + decoder, 1 = middle block, then the encoder
     # stages deepest first (EfficientUNetND input_blocks / UNetDiffusersND conv_in + down_blocks), and last the

@@ -11,8 +11,6 @@ self-tests call the blocks this way (``src/nn/blocks/residual.py:160-215``,
 """
 from __future__ import annotations
 
-import weakref
-
 import torch
 
 from . import ops
@@ -50,30 +48,13 @@ def linear_forward(lin, x: torch.Tensor) -> torch.Tensor:
     return ops.linear(x.float().contiguous(), lin.weight.detach(), lin.bias.detach() if lin.bias is not None else None)
 
 
-def _block_engine_cls():
-    from .engine import UNetEngine, WeightCache
-
-    class BlockEngine(UNetEngine):
-        """One-block engine: the UNet engine's layer methods (res_block / attention / cross_attention) on a
-        lone block module (no grouped emb projections, no time MLP)."""
-
-        def __init__(self, block):   # UNetEngine.__init__'s UNet-model checks do not apply
-            self._model = weakref.ref(block)
-            self.kind = "block"
-            self.wc = WeightCache()
-            self._tt = None
-            self.gl, self.gl_slot = None, {}
-            self._head_bwd = None
-            self.dims1 = False
-            self._wq = ops.WgradQueue()
-
-    return BlockEngine
-
-
 def _block_engine(block):
+    """One-block engine: the layer methods (res_block / attention / cross_attention) on a lone block module
+    (no grouped emb projections, no time MLP)."""
     eng = getattr(block, "_fmd_block_engine", None)
     if eng is None:
-        eng = _block_engine_cls()(block)
+        from .engine import LayerEngine
+        eng = LayerEngine(block, dims1=False)
         object.__setattr__(block, "_fmd_block_engine", eng)
     return eng
 

@@ -2,8 +2,8 @@
 VQVAE: encoder -> HIP quantizer -> decoder, ``vq_forward``).
 
 Walks the reference module trees (``src/nn/modules/vae/encoder.py:139-158``,
-``decoder.py:133-160``, ``src/models/vae/kl.py:116-128``) with the UNet engine's layer
-implementations (``fmdiff.runtime.engine``): ResBlocks as two fused implicit-GEMM / halo convs
+``decoder.py:133-160``, ``src/models/vae/kl.py:116-128``) with the layer
+methods of ``fmdiff.runtime.engine.LayerEngine``: ResBlocks as two fused implicit-GEMM / halo convs
 with GroupNorm+SiLU in the gather and skip + residual in the epilogue, stride-2 / nearest-x2
 resampling inside the convs, the mid-block SpatialSelfAttention on the attention kernels, and
 GroupNorm -> SiLU -> conv_out on the head kernels.  ``quant_conv`` (1x1, pointwise after conv_out) is
@@ -13,29 +13,20 @@ Forward / inference only: VAE training is outside the hot path.
 """
 from __future__ import annotations
 
-import weakref
-
 import torch
 
 from . import ops
-from .engine import CPAD, Act, Ctx, UNetEngine, WeightCache
+from .engine import CPAD, Act, Ctx, LayerEngine
 from ..nn.params import Conv, Identity
 
 F32 = torch.float32
 
 
-class VAEEngine(UNetEngine):
+class VAEEngine(LayerEngine):
     def __init__(self, module):
-        self._model = weakref.ref(module)
-        self.kind = "vae"
-        self.wc = WeightCache()
-        self._tt = None
-        self.gl, self.gl_slot = None, {}
-        self._fold = None
+        super().__init__(module, dims1=False)   # 2-D models only (spatial_dims checked on entry)
+        self._fold = None       # conv_out with quant_conv folded in (_folded_out)
         self._fold_key = None
-        self._head_bwd = None
-        self.dims1 = False   # the VAE engine runs 2-D models only (spatial_dims checked on entry)
-        self._wq = ops.WgradQueue()   # forward only: stays empty
 
     def _ctx(self, part, N, dev):
         emb = None
