@@ -62,6 +62,15 @@ class AutoencoderKL(BaseVAE):
             z = z / LATENT_SCALE
         return get_vae_engine(self).decode(z)
 
+    def forward_train(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None, sample_posterior: bool = True):
+        """The training forward on the engine: ``(rec, z, kl)`` with ``rec`` NCHW fp32 the raw decoder output,
+        ``z`` NCHW fp32 the sampled latent (the mode with ``sample_posterior=False``) and ``kl`` ``[N]`` the
+        per-sample KL, all connected to the parameters by autograd (the written-out backward accumulates into
+        ``.grad``).  ``eps``: the posterior noise, fp32 ``[N, embed_dim, h, w]``; None: drawn on the device.
+        2-D, eager, ROCm device tensors only; ``forward`` / ``encode`` / ``decode`` are unchanged."""
+        from ...runtime.vae_engine import vae_forward_train
+        return vae_forward_train(self, x, eps, sample_posterior)
+
     def forward(self, x: torch.Tensor, sample_posterior: bool = True):
         posterior = self.encode(x, normalize=False)
         z = posterior.sample() if sample_posterior else posterior.mode()

@@ -1,7 +1,8 @@
 """VAE trainer pieces (reference ``src/pipelines/train/vae_lib.py``): the scheduler factory, the discriminator
 gate and the training criterion as one object over the HIP loss kernels (``fmdiff.nn.losses.vae``,
-``csrc/vae_loss.hip``).  The trainer loop itself is not built: it needs the encoder / decoder backward, the
-discriminator and the perceptual loss."""
+``csrc/vae_loss.hip``), and one whole AutoencoderKL optimizer step on the engine (``VAETrainStep``).  The trainer
+loop itself is not built: the datasets, checkpoints and images around the step, the discriminator and the
+perceptual loss are missing."""
 from __future__ import annotations
 
 from typing import Any, Dict, Optional
@@ -10,7 +11,7 @@ import torch
 
 from ...nn.losses.vae import discriminator_hinge_loss, generator_hinge_loss, recon_loss
 
-__all__ = ["VAECriterion", "train"]
+__all__ = ["VAECriterion", "VAETrainStep", "train"]
 
 TOTALS_KEYS = ("loss", "recon", "kl", "perceptual", "g_gan", "d_gan", "vq")
 
@@ -123,7 +124,106 @@ class VAECriterion:
         return discriminator_hinge_loss(real_pred, fake_pred)
 
 
+class VAETrainStep:
+    """One optimizer step of AutoencoderKL on the engine, the body of the reference's loop
+    (``vae_lib.py:198-316``) without AMP, microbatching, discriminator or perceptual terms::
+
+        inputs = model.image_to_model_range(raw_images)
+        rec, z, kl = model.forward_train(inputs, eps)
+        out = VAECriterion(...)(rec, raw_images, kl=kl, global_step=global_step)
+        out["loss"].backward()
+        AdamW(lr, weight_decay)                      # torch defaults otherwise, as the reference builds it
+
+    Parameters, gradients and Adam moments are flat fp32 buffers (``FlatParams``), the optimizer is one
+    ``ops.adamw`` launch, and because it writes the parameters through raw pointers the step then re-derives the
+    engine's bf16 weight layouts and the folded quant_conv.  ``global_step`` is a host integer used for
+    ``kl_scale`` and Adam's bias correction only; nothing in ``step`` synchronises with the host."""
+
+    def __init__(self, model, training_cfg: Dict[str, Any], model_cfg: Optional[Dict[str, Any]] = None, *,
+                 lr: Optional[float] = None, weight_decay: Optional[float] = None, betas=(0.9, 0.999),
+                 eps: float = 1e-8) -> None:
+        from ...runtime.vae_engine import get_vae_engine
+        from .fused import FlatParams
+        self.criterion = VAECriterion(training_cfg, model_cfg)
+        if self.criterion.gan_weight > 0:
+            raise NotImplementedError("GAN discriminators (VAE training) are outside the fmdiff hot path; set "
+                                      "gan_weight to 0")
+        if self.criterion.effective_codebook_weight != 0.0 or hasattr(model, "codebook"):
+            raise NotImplementedError("VAETrainStep trains AutoencoderKL; the VQVAE trunk backward is not built "
+                                      "(DESIGN.md section 7)")
+        self.model = model
+        self.eng = get_vae_engine(model)
+        self.eng.check_trainable()
+        self.lr = float(training_cfg.get("learning_rate", 1e-4) if lr is None else lr)
+        self.weight_decay = float(training_cfg.get("weight_decay", 0.0) if weight_decay is None else weight_decay)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.flat = FlatParams(model)
+        self.m = torch.zeros_like(self.flat.data)
+        self.v = torch.zeros_like(self.flat.data)
+        self.global_step = 0
+        self.eng.invalidate_weights()   # the parameters moved into the flat buffer
+
+    def step(self, raw_images: torch.Tensor, eps: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """``raw_images``: the batch in [0, 1], NCHW fp32 on the device; ``eps``: the posterior noise (None: drawn
+        on the device).  Returns VAECriterion's totals as device scalars (``loss`` detached)."""
+        self.flat.grad.zero_()
+        inputs = self.model.image_to_model_range(raw_images)
+        rec, _, kl = self.model.forward_train(inputs, eps, sample_posterior=True)
+        out = self.criterion(rec, raw_images, kl=kl, global_step=self.global_step)
+        out["loss"].backward()
+        out["loss"] = out["loss"].detach()
+        self.global_step += 1
+        from ...runtime import ops
+        ops.adamw(self.flat.data, self.flat.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
+                  self.weight_decay, self.global_step)
+        self.eng.invalidate_weights()
+        return out
+
+    def state_dict(self) -> Dict[str, Any]:
+        """The optimizer state in ``torch.optim.AdamW.state_dict()`` form (state keyed by the index in
+        ``model.parameters()``) plus ``global_step``."""
+        params = list(self.model.parameters())
+        state = {}
+        if self.global_step > 0:
+            for i, p in enumerate(params):
+                off, n = self.flat.offsets[id(p)]
+                state[i] = {"step": torch.tensor(float(self.global_step)),
+                            "exp_avg": self.m[off:off + n].view_as(p).detach().cpu().clone(),
+                            "exp_avg_sq": self.v[off:off + n].view_as(p).detach().cpu().clone()}
+        group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay,
+                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
+                 "fused": None, "decoupled_weight_decay": True, "params": list(range(len(params)))}
+        return {"state": state, "param_groups": [group], "global_step": self.global_step}
+
+    def load_state_dict(self, sd: Dict[str, Any]) -> None:
+        """Inverse of ``state_dict`` (also takes a torch AdamW state of the same model)."""
+        params = list(self.model.parameters())
+        st = sd.get("state", {})
+        steps = 0
+        with torch.no_grad():
+            self.m.zero_()
+            self.v.zero_()
+            for i, p in enumerate(params):
+                e = st.get(i) if i in st else st.get(str(i))
+                if not e:
+                    continue
+                off, n = self.flat.offsets[id(p)]
+                self.m[off:off + n].copy_(torch.as_tensor(e["exp_avg"]).reshape(-1))
+                self.v[off:off + n].copy_(torch.as_tensor(e["exp_avg_sq"]).reshape(-1))
+                steps = max(steps, int(float(torch.as_tensor(e["step"]))))
+        self.global_step = int(sd.get("global_step", steps))
+        groups = sd.get("param_groups") or []
+        if groups:
+            g = groups[0]
+            self.lr = float(g.get("lr", self.lr))
+            self.weight_decay = float(g.get("weight_decay", self.weight_decay))
+            self.betas = tuple(float(b) for b in g.get("betas", self.betas))
+            self.eps = float(g.get("eps", self.eps))
+
+
 def train(dataset, json_path, val_dataset=None, resume=None) -> None:
-    raise NotImplementedError("The VAE trainer loop is not built: it needs the encoder / decoder backward, the "
-                              "discriminator and the perceptual loss (DESIGN.md section 7).  The criterion it "
-                              "would call is VAECriterion; the quantizer half is VectorQuantizer*.quantize_train.")
+    raise NotImplementedError("The VAE trainer loop is not built: the datasets, checkpoints and sample images "
+                              "around the step, the discriminator and the perceptual loss are still missing "
+                              "(DESIGN.md section 7).  One AutoencoderKL optimizer step is VAETrainStep; the "
+                              "criterion it calls is VAECriterion; the quantizer half is "
+                              "VectorQuantizer*.quantize_train.")

@@ -554,7 +554,8 @@ class LayerEngine:
                          pro=bool(kw.get("pro")),
                          exact_weight=Kpad is None and w.shape[1] == Cin and w.dim() == len(sp) + 2)
         if stride == 1:
-            base, tiled = self._wts(w, 3, route == "halo", Kpad, None)
+            # a channel-padded input (the VAE decoder's staged latent): zero weight rows for its padding channels
+            base, tiled = self._wts(w, 3, route == "halo", Kpad, Cin if w.shape[1] < Cin else None)
             return ops.conv(dy, Cin, base, ks=3, stride=1, pad=1, out_hw_=sp, wgt_tiled=tiled, **kw)
         if route == "d2s":
             # transposed stride-2 gather onto the depth-to-space view, on the halo kernel (3-D: 8 classes)

@@ -1982,3 +1982,75 @@ def gauss_backward(moments, E: int, eps, g_z, g_kl, *, ldd: Optional[int] = None
     _lib.call("fmd_gauss_backward", _p(moments), ldm, N, E, P, _p(eps), _p(g_z), _p(g_kl), _p(dm), ldd, _p(db),
               int(ldb or 0), stream())
     return dm, db
+
+
+# ------------------------------------------------------------------ latent 1x1 conv backward (csrc/pointwise_bwd.hip)
+POINTWISE_ROWS, POINTWISE_MAXC = 512, 8   # FMD_POINTWISE_ROWS / _MAXC
+
+
+def pointwise_bwd(dy, x, W, *, channels_last: bool = False, ldg: Optional[int] = None, want_g: bool = True,
+                  dW=None, db=None, accumulate: bool = False, out=None, ws=None):
+    """Backward of the latent 1x1 conv ``y = W x + b`` (AutoencoderKL's ``post_quant_conv``) in one launch plus the
+    finishing launch of the sums.  ``dy`` bf16 channels-last ``[N, *spatial, >= Z]`` and ``x`` bf16 channels-last
+    ``[N, *spatial, >= E]`` (the staged latent of ``gauss_sample_kl``); channels past Z / E never enter a result.
+    ``W`` fp32 ``[Z, E]`` (or ``[Z, E, 1, 1]``), Z and E at most ``POINTWISE_MAXC``.
+
+    Returns ``(g, dW, db)``: ``g`` fp32, channels-first ``[N, E, *spatial]`` (the ``g_z`` of ``gauss_backward``) or
+    with ``channels_last`` ``[N, *spatial, ldg]`` (padding channels zero; default ``ldg``: E rounded up to 8), into
+    ``out`` when given, None without ``want_g``; ``dW`` ``[Z, E]`` / ``db`` ``[Z]``: the fp32 tensors passed in
+    (``x`` may be None without them), written, or with ``accumulate`` added to.  Nothing synchronises."""
+    what = "pointwise_bwd"
+    _need_cuda(dy, what)
+    if W.dim() not in (2, 4) or (W.dim() == 4 and tuple(W.shape[2:]) != (1, 1)):
+        raise ValueError(f"{what}: W is [Z, E] or [Z, E, 1, 1], got {tuple(W.shape)}")
+    Z, E = int(W.shape[0]), int(W.shape[1])
+    _f32c(W, what, "W")
+    sums = dW is not None or db is not None
+    for t, name, cmin in ((dy, "dy", Z), (x, "x", E)):
+        if t is None and name == "x" and not sums:
+            continue
+        if t is None:
+            raise ValueError(f"{what}: dW / db need x")
+        _need_cuda(t, what)
+        if t.dtype != BF16 or not t.is_contiguous() or t.dim() < 3 or t.shape[-1] < cmin:
+            raise RuntimeError(f"{what}: {name} must be contiguous bf16 [N, *spatial, >= {cmin}], got {t.dtype} "
+                               f"{tuple(t.shape)}")
+    if x is not None and tuple(x.shape[:-1]) != tuple(dy.shape[:-1]):
+        raise ValueError(f"{what}: dy {tuple(dy.shape)} and x {tuple(x.shape)} differ in their rows")
+    N, sp = int(dy.shape[0]), tuple(int(v) for v in dy.shape[1:-1])
+    P = 1
+    for v in sp:
+        P *= v
+    need = int(_lib.lib().fmd_pointwise_bwd_workspace(N * P, Z, E))
+    if need < 0:
+        raise ValueError(f"{what}: Z = {Z}, E = {E} beyond the kernel's limit of {POINTWISE_MAXC} channels, an "
+                         f"empty tensor or a shape beyond its grid, {tuple(dy.shape)}")
+    for t, name, shape in ((dW, "dW", (Z, E)), (db, "db", (Z,))):
+        if t is not None:
+            _f32c(t, what, name)
+            if t.numel() != Z * (E if name == "dW" else 1) or tuple(t.shape[:len(shape)]) != shape:
+                raise ValueError(f"{what}: {name} must be {shape}, got {tuple(t.shape)}")
+    g = None
+    if want_g:
+        if channels_last:
+            ldg = int(ldg or max(8, -(-E // 8) * 8))
+            if ldg < E:
+                raise ValueError(f"{what}: ldg {ldg} below the channel count {E}")
+            shape = (N, *sp, ldg)
+        else:
+            shape = (N, E, *sp)
+        g = out
+        if g is None:
+            g = torch.empty(shape, device=dy.device, dtype=F32)
+        else:
+            _f32c(g, what, "out")
+            if tuple(g.shape) != shape:
+                raise RuntimeError(f"{what}: out must be {shape}, got {tuple(g.shape)}")
+    elif not sums:
+        raise ValueError(f"{what}: nothing asked for")
+    if sums:
+        ws = _ws(ws, need, dy.device, what)
+    _lib.call("fmd_pointwise_bwd", _p(dy), int(dy.shape[-1]), _p(x) if sums else None,
+              int(x.shape[-1]) if sums else 0, _p(W), N, P, Z, E, _p(g), int(bool(channels_last)), int(ldg or 0),
+              _p(dW), _p(db), int(bool(accumulate)), _p(ws) if sums else None, stream())
+    return g, dW, db

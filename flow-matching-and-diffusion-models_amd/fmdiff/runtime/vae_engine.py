@@ -9,7 +9,12 @@ resampling inside the convs, the mid-block SpatialSelfAttention on the attention
 GroupNorm -> SiLU -> conv_out on the head kernels.  ``quant_conv`` (1x1, pointwise after conv_out) is
 folded into conv_out's weights, so ``encode`` ends in one head launch; ``post_quant_conv`` runs as a
 1x1 conv before the decoder (folding it into conv_in would be wrong at the zero-padded border).
-Forward / inference only: VAE training is outside the hot path.
+
+AutoencoderKL also trains here (2-D, eager): ``train_encode`` / ``train_decode`` walk the same trunks under a
+tape, their backwards run it the way ``UNetEngine.backward`` does, the gradient of the folded conv is unfolded
+exactly onto conv_out and quant_conv (``unfold_quant_grads``), and post_quant_conv's backward is one VALU launch
+(``ops.pointwise_bwd``, csrc/pointwise_bwd.hip).  ``vae_forward_train`` ties them to autograd.  The VQVAE trunk
+backward is not built.
 """
 from __future__ import annotations
 
@@ -17,6 +22,7 @@ import torch
 
 from . import ops
 from .engine import CPAD, Act, Ctx, LayerEngine
+from ..nn.blocks.residual import ResBlockND
 from ..nn.params import Conv, Identity
 
 F32 = torch.float32
@@ -28,11 +34,14 @@ class VAEEngine(LayerEngine):
         self._fold = None       # conv_out with quant_conv folded in (_folded_out)
         self._fold_key = None
 
-    def _ctx(self, part, N, dev):
+    def _ctx(self, part, N, dev, save=False):
         emb = None
         if part.emb_channels is not None:   # the reference feeds zeros (encoder.py:141-144)
             emb = torch.zeros((N, part.emb_channels), device=dev, dtype=F32)
-        return Ctx(emb, False, N)
+        ctx = Ctx(emb, False, N)
+        if save:   # training walks have no embedding (check_trainable): a tape, no demb
+            ctx.tape = []
+        return ctx
 
     def _stage(self, x):
         """NCHW fp32 -> NHWC bf16 with CPAD-padded channels."""
@@ -46,10 +55,10 @@ class VAEEngine(LayerEngine):
             h = self.attention(part.mid_attn, h, ctx)
         return self.res_block(part.mid_block2, [h], ctx)
 
-    def _encoder_trunk(self, enc, x):
+    def _encoder_trunk(self, enc, x, save=False):
         if enc.spatial_dims != 2:
             raise NotImplementedError("fmdiff VAE engine: spatial_dims=2")
-        ctx = self._ctx(enc, x.shape[0], x.device)
+        ctx = self._ctx(enc, x.shape[0], x.device, save)
         h = self.conv_layer(enc.conv_in.conv, Act(self._stage(x), need_grad=False), ctx)
         for stage in enc.downs:
             for i, blk in enumerate(stage.blocks):
@@ -160,6 +169,175 @@ class VAEEngine(LayerEngine):
             eps = torch.randn((mom.shape[0], E, *mom.shape[1:-1]), device=mom.device, dtype=F32)
         z, kl, zs = ops.gauss_sample_kl(mom, E, eps, Cp=max(CPAD, -(-E // 8) * 8))
         return self._decode_staged(zs), z, kl
+
+
+    # ------------------------------------------------------------ training (AutoencoderKL, 2-D, eager)
+    def check_trainable(self):
+        """Refuse what the trunk backward is not built (or not checked) for."""
+        vae = self.m
+        what = "fmdiff VAE training"
+        if not hasattr(vae, "quant_conv") or hasattr(vae, "codebook"):
+            raise NotImplementedError(f"{what}: AutoencoderKL only (the VQVAE trunk backward is not built, DESIGN.md 7)")
+        enc, dec, pq = vae.encoder, vae.decoder, vae.post_quant_conv.conv
+        if enc.spatial_dims != 2 or dec.spatial_dims != 2:
+            raise NotImplementedError(f"{what}: spatial_dims=2")
+        if dec.tanh_out:
+            raise NotImplementedError(f"{what}: tanh_out decoders")
+        if enc.emb_channels is not None or dec.emb_channels is not None:
+            raise NotImplementedError(f"{what}: emb_channels (no reference path to check the embedding against)")
+        if any(isinstance(mod, ResBlockND) and float(mod.dropout or 0.0) > 0 for mod in vae.modules()):
+            raise NotImplementedError(f"{what}: dropout > 0")
+        if max(pq.in_channels, pq.out_channels) > ops.POINTWISE_MAXC:
+            raise NotImplementedError(f"{what}: z_channels and embed_dim up to {ops.POINTWISE_MAXC} (the latent 1x1 "
+                                      f"backward kernel), got {pq.out_channels} and {pq.in_channels}")
+
+    def ensure_grads(self):
+        for p in self.m.parameters():
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+
+    def invalidate_weights(self):
+        """After an optimizer that writes the parameters through raw pointers (no ``_version`` bump): re-derive
+        the bf16 kernel layouts and drop the folded conv_out, which is rebuilt from the masters on its next use."""
+        self._fold_key = None
+        if self._fold is not None:   # before the layouts: the fold's own bf16 copies are derived from it
+            self._folded_out(self.m)
+        super().invalidate_weights()
+
+    def _run_backward(self, head_bwd, dpred, tape):
+        """What UNetEngine.backward does around its tape: batched GroupNorm folds, the head first, the tape in
+        reverse, every weight gradient landed on return."""
+        ops.gb_defer()
+        try:
+            head_bwd(dpred)
+            for fn in reversed(tape):
+                fn()
+            self._join()
+        except BaseException:
+            self._wq.clear()   # a failed backward leaves no weight gradient queued for the next one
+            raise
+        finally:
+            ops.gb_flush()
+        self._join()
+
+    def train_encode(self, x):
+        """Encoder + folded quant_conv under a tape: (fp32 NHWC moments [N, h, w, Kp], state for the backward)."""
+        self.check_trainable()
+        vae = self.m
+        enc = vae.encoder
+        h, ctx = self._encoder_trunk(enc, x, save=True)
+        fold = self._folded_out(vae)
+        mom = self.head(enc.norm_out, fold, h, ctx)
+        head_bwd, self._head_bwd = self._head_bwd, None   # one slot: the decoder's head would overwrite it
+        return mom, (ctx, head_bwd)
+
+    def train_encode_backward(self, state, dmom):
+        """``dmom``: bf16 NHWC gradient of the moments (padding channels zero).  Accumulates into ``.grad`` of the
+        encoder and of quant_conv (the fold's gradient unfolded exactly)."""
+        ctx, head_bwd = state
+        vae = self.m
+        fold = self._fold
+        for p in (fold.weight, fold.bias):
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        self._run_backward(head_bwd, dmom, ctx.tape)
+        ctx.tape = None
+        co, qc = vae.encoder.conv_out.conv, vae.quant_conv.conv
+        dwo, dbo, dwq, dbq = unfold_quant_grads(qc.weight.detach().reshape(qc.out_channels, -1), co.weight.detach(),
+                                                co.bias.detach(), fold.weight.grad, fold.bias.grad)
+        co.weight.grad.add_(dwo)
+        co.bias.grad.add_(dbo)
+        qc.weight.grad.add_(dwq.view_as(qc.weight))
+        qc.bias.grad.add_(dbq)
+        fold.weight.grad.zero_()
+        fold.bias.grad.zero_()
+
+    def train_decode(self, zs):
+        """post_quant_conv + decoder under a tape from the staged latent: (fp32 NHWC output, state)."""
+        self.check_trainable()
+        vae = self.m
+        dec, pq = vae.decoder, vae.post_quant_conv.conv
+        Kp = max(CPAD, -(-pq.out_channels // 8) * 8)
+        hz, _ = ops.conv(zs, Kp, self.wc.get(pq.weight, 0, Kp, zs.shape[-1]), ks=1, pad=0,
+                         bias=self.wc.padded(pq.bias, Kp))
+        ctx = self._ctx(dec, zs.shape[0], zs.device, save=True)
+        hin = Act(hz, need_grad=True)
+        out = self._decoder_trunk(dec, hin, ctx)
+        head_bwd, self._head_bwd = self._head_bwd, None
+        return out, (ctx, head_bwd, hin, zs)
+
+    def train_decode_backward(self, state, dpred):
+        """``dpred``: bf16 NHWC gradient of the decoder output.  Accumulates into ``.grad`` of the decoder and of
+        post_quant_conv; returns ``g_z``, the fp32 channels-first gradient of the latent."""
+        ctx, head_bwd, hin, zs = state
+        pq = self.m.post_quant_conv.conv
+        self._run_backward(head_bwd, dpred, ctx.tape)
+        ctx.tape = None
+        g_z, _, _ = ops.pointwise_bwd(hin.grad, zs, pq.weight.detach().reshape(pq.out_channels, pq.in_channels),
+                                      dW=pq.weight.grad, db=pq.bias.grad, accumulate=True)
+        return g_z
+
+
+def unfold_quant_grads(wq, w_out, b_out, dwf, dbf):
+    """Gradients of ``conv_out`` and ``quant_conv`` from those of their fold ``W_f = W_q . W_out``,
+    ``b_f = W_q b_out + b_q`` (``VAEEngine._folded_out``).  ``wq`` [O, Z], ``w_out`` [Z, C, kh, kw], ``b_out`` [Z],
+    ``dwf`` [O, C, kh, kw], ``dbf`` [O].  Returns ``(dW_out, db_out, dW_q [O, Z], db_q)``; tensors in, tensors out."""
+    dw_out = torch.einsum("oz,ochw->zchw", wq, dwf)
+    db_out = wq.t() @ dbf
+    dwq = torch.einsum("ochw,zchw->oz", dwf, w_out) + dbf[:, None] * b_out[None, :]
+    return dw_out, db_out, dwq, dbf.clone()
+
+
+class _VAEEncodeFunction(torch.autograd.Function):
+    """x -> the channels-last fp32 moments; parameter gradients are written into ``.grad`` (as _UNetFunction)."""
+
+    @staticmethod
+    def forward(fctx, x, engine, *params):
+        mom, state = engine.train_encode(x)
+        fctx.engine, fctx.state = engine, state
+        return mom
+
+    @staticmethod
+    def backward(fctx, gmom):
+        eng = fctx.engine
+        eng.ensure_grads()
+        eng.train_encode_backward(fctx.state, gmom.contiguous().to(torch.bfloat16))
+        fctx.state = None
+        return (None, None) + tuple(None for _ in eng.m.parameters())
+
+
+class _VAEDecodeFunction(torch.autograd.Function):
+    """(z, its staged bf16 copy) -> rec NCHW fp32.  ``z`` only carries the graph: the decoder reads the staged
+    operand.  Backward runs the decoder's tape, then the latent 1x1's backward, and returns ``g_z``."""
+
+    @staticmethod
+    def forward(fctx, z, zs, engine, *params):
+        out, state = engine.train_decode(zs)
+        fctx.engine, fctx.state, fctx.kpad = engine, state, out.shape[-1]
+        return ops.nhwc_to_nchw(out, engine.m.decoder.conv_out.conv.out_channels)
+
+    @staticmethod
+    def backward(fctx, grec):
+        eng = fctx.engine
+        eng.ensure_grads()
+        g_z = eng.train_decode_backward(fctx.state, ops.nchw_to_nhwc(grec.contiguous(), fctx.kpad))
+        fctx.state = None
+        return (g_z, None, None) + tuple(None for _ in eng.m.parameters())
+
+
+def vae_forward_train(module, x, eps=None, sample_posterior=True):
+    """AutoencoderKL.forward_train: (rec NCHW fp32, z NCHW fp32, kl [N]), connected to the parameters by autograd."""
+    from ..nn.modules.vae import reparameterize_kl
+    eng = get_vae_engine(module)
+    eng.check_trainable()
+    ops._need_cuda(x, f"{type(module).__name__}.forward_train")
+    params = list(module.parameters())
+    E = module.post_quant_conv.conv.in_channels
+    mom = _VAEEncodeFunction.apply(x, eng, *params)
+    z, kl, zs = reparameterize_kl(mom, eps, sample_posterior, channels_last=True, embed_dim=E,
+                                  staged_channels=max(CPAD, -(-E // 8) * 8))
+    rec = _VAEDecodeFunction.apply(z, zs, eng, *params)
+    return rec, z, kl
 
 
 def get_vae_engine(module) -> VAEEngine:

@@ -780,6 +780,25 @@ int fmd_gauss_backward(const float* moments, int32_t ldm, int32_t N, int32_t E, 
                        const float* g_z, const float* g_kl, float* d_moments, int32_t ldd, void* d_moments_bf16,
                        int32_t ldb, fmd_stream_t s);
 
+/* ---- Backward of the latent 1x1 conv (csrc/pointwise_bwd.hip): AutoencoderKL's post_quant_conv,
+ * y[m][z] = b[z] + sum_e W[z][e] x[m][e], 1 <= Z, E <= FMD_POINTWISE_MAXC, M = N * P rows.
+ *   dy bf16 [M][ldy] (channels >= Z never enter a result), x bf16 [M][ldx] (the staged latent that
+ *   fmd_gauss_sample_kl wrote; channels >= E likewise), W fp32 [Z][E], the master weight.
+ *   g (optional) fp32: g[m][e] = sum_z dy[m][z] W[z][e], added in fp64 in ascending z and rounded once;
+ *     g_channels_last == 0: channels-first [N][E][P], the g_z of fmd_gauss_backward;
+ *     else [M][ldg] with the channels >= E written as 0.
+ *   dW[z][e] = sum_m dy[m][z] x[m][e] and db[z] = sum_m dy[m][z] (each optional; x and ws needed by either): fp64
+ *     sums in a fixed order, rounded once to fp32, then stored (accumulate == 0) or added in fp32 to the value there.
+ * The same bits on every run: no atomics, FMD_POINTWISE_ROWS rows per workgroup, one fp64 partial per workgroup
+ * and sum in ws, a finishing launch.  fmd_pointwise_bwd_workspace: bytes of ws.  Z or E beyond the limit, empty
+ * shapes, strides below the channel counts, nothing asked for: -1 from both. */
+#define FMD_POINTWISE_ROWS 512
+#define FMD_POINTWISE_MAXC 8
+int64_t fmd_pointwise_bwd_workspace(int64_t M, int32_t Z, int32_t E);
+int fmd_pointwise_bwd(const void* dy, int32_t ldy, const void* x, int32_t ldx, const float* W, int32_t N, int64_t P,
+                      int32_t Z, int32_t E, float* g, int32_t g_channels_last, int32_t ldg, float* dW, float* db,
+                      int32_t accumulate, void* ws, fmd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
