@@ -213,6 +213,13 @@ __global__ __launch_bounds__(256) void vq_segsum_kernel(const float* __restrict_
   }
 }
 
+// The code of row m, clamped into the codebook (a code is never out of range after fmd_vq_finalize; the clamp keeps
+// a corrupted one from reading outside the codebook).  Shared by the two latent-gradient kernels below.
+FMD_DEV long long vq_code_row(const long long* __restrict__ codes, long long m, int K) {
+  const long long k = codes[m];
+  return k < 0 ? 0 : (k >= K ? K - 1 : k);
+}
+
 // dz = g_zq + coef (z - q) on the first D channels, zero on the rest; coef = (g_loss * c) * scale.  E null: the
 // rows of z already hold z - q.
 __global__ __launch_bounds__(256) void vq_backward_kernel(const float* __restrict__ z, int ldz, int M, int K, int D,
@@ -228,14 +235,80 @@ __global__ __launch_bounds__(256) void vq_backward_kernel(const float* __restric
     float o = 0.f;
     if (d < D) {
       float diff = z[(size_t)m * ldz + d];
-      if (E) {
-        long long k = codes[m];
-        k = k < 0 ? 0 : (k >= K ? K - 1 : k);
-        diff = diff - E[(size_t)k * D + d];
-      }
+      if (E) diff = diff - E[(size_t)vq_code_row(codes, m, K) * D + d];
       o = fmaf(coef, diff, g ? g[(size_t)m * ldg + d] : 0.f);
     }
     dz[i] = o;
+  }
+}
+
+// n <= 8 consecutive floats of a row into v (the rest zero).  vec: the row is 16-byte aligned, so a whole group
+// of 8 is two 16-byte loads; a partial group reads its valid channels only, one by one.
+FMD_DEV void vq_load8(const float* __restrict__ p, int n, bool vec, float* v) {
+  if (vec && n == 8) {
+    const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  } else {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = u < n ? p[u] : 0.f;
+  }
+}
+
+// The latent join of the VQVAE backward: the arithmetic of vq_backward_kernel, element for element, with g read as
+// the 1x1 data gradient left it (bf16 or fp32, channels-last, own row stride) and dz stored as the bf16 operand the
+// encoder head's backward reads: rounded once, to nearest even, channels D .. lddz-1 exact zeros.
+// A thread owns 8 consecutive channels of a row (one 16-byte store; 16- or 2 x 16-byte loads when the group is
+// whole), consecutive lanes consecutive groups, rows grid-strided.  Channels >= D of g, z and E are never read.
+template <bool GF32>
+__global__ __launch_bounds__(256) void vq_join_bwd_kernel(const float* __restrict__ z, int ldz, int zvec, int M,
+                                                          int K, int D, const long long* __restrict__ codes,
+                                                          const float* __restrict__ E, int evec,
+                                                          const void* __restrict__ g, int ldg,
+                                                          const float* __restrict__ gl, float c, float scale,
+                                                          bf16r* __restrict__ dz, int lddz) {
+  const float coef = ((gl ? gl[0] : 0.f) * c) * scale;
+  const int G = lddz >> 3;
+  const long long total = (long long)M * G;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long m = i / G;
+    const int d0 = (int)(i - m * G) << 3;
+    const int n = D - d0 < 8 ? D - d0 : 8;   // <= 0: a group of padding channels only
+    u32x4 o = {0u, 0u, 0u, 0u};
+    if (n > 0) {
+      float diff[8], gv[8];
+      vq_load8(z + (size_t)m * ldz + d0, n, zvec, diff);
+      if (E) {
+        float e[8];
+        vq_load8(E + (size_t)vq_code_row(codes, m, K) * D + d0, n, evec, e);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) diff[u] = diff[u] - e[u];
+      }
+      if (!g) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) gv[u] = 0.f;
+      } else if (GF32) {
+        vq_load8((const float*)g + (size_t)m * ldg + d0, n, true, gv);
+      } else {
+        const bf16r* gp = (const bf16r*)g + (size_t)m * ldg + d0;
+        if (n == 8) {
+          const u32x4 w = *(const u32x4*)gp;
+          gv[0] = bf_lo(w.x); gv[1] = bf_hi(w.x); gv[2] = bf_lo(w.y); gv[3] = bf_hi(w.y);
+          gv[4] = bf_lo(w.z); gv[5] = bf_hi(w.z); gv[6] = bf_lo(w.w); gv[7] = bf_hi(w.w);
+        } else {
+#pragma unroll
+          for (int u = 0; u < 8; ++u) gv[u] = u < n ? bf2f(gp[u]) : 0.f;
+        }
+      }
+      float r[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) r[u] = u < n ? fmaf(coef, diff[u], gv[u]) : 0.f;
+      o.x = pack2(r[0], r[1]);
+      o.y = pack2(r[2], r[3]);
+      o.z = pack2(r[4], r[5]);
+      o.w = pack2(r[6], r[7]);
+    }
+    *(u32x4*)(dz + (size_t)m * lddz + d0) = o;
   }
 }
 
@@ -289,5 +362,25 @@ extern "C" int fmd_vq_backward(const float* z, int32_t ldz, int32_t M, int32_t K
   const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   hipLaunchKernelGGL(vq_backward_kernel, dim3(grid), dim3(256), 0, (hipStream_t)s, z, ldz, M, K, D,
                      (const long long*)codes, embedding, g_zq, ldg, g_loss, c, scale, dz, lddz);
+  return (int)hipGetLastError();
+}
+
+extern "C" int fmd_vq_join_bwd(const float* z, int32_t ldz, int32_t M, int32_t K, int32_t D, const int64_t* codes,
+                               const float* embedding, const void* g_zq, int32_t g_f32, int32_t ldg,
+                               const float* g_loss, float c, float scale, void* dz, int32_t lddz, fmd_stream_t s) {
+  if (!z || !dz || M < 1 || K < 1 || D < 1 || D > VT_DMAX || M > (1 << 30) || ldz < D || lddz < D || (lddz & 7) ||
+      ((uintptr_t)dz & 15) || (g_zq && (ldg < D || (ldg & 7) || ((uintptr_t)g_zq & 15))) || (g_f32 & ~1) ||
+      (embedding && !codes))
+    return -1;
+  const int zvec = !(ldz & 3) && !((uintptr_t)z & 15);
+  const int evec = embedding && !(D & 3) && !((uintptr_t)embedding & 15);
+  const long long total = (long long)M * (lddz >> 3);
+  const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  if (g_f32)
+    hipLaunchKernelGGL(vq_join_bwd_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)s, z, ldz, zvec, M, K, D,
+                       (const long long*)codes, embedding, evec, g_zq, ldg, g_loss, c, scale, (bf16r*)dz, lddz);
+  else
+    hipLaunchKernelGGL(vq_join_bwd_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)s, z, ldz, zvec, M, K, D,
+                       (const long long*)codes, embedding, evec, g_zq, ldg, g_loss, c, scale, (bf16r*)dz, lddz);
   return (int)hipGetLastError();
 }

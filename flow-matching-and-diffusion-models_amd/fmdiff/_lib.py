@@ -221,6 +221,7 @@ SIGNATURES = {
     "fmd_vq_ema_update": [p, i32, i32, i32, i32, p, p, f32, f32, f32, f32, p, p, p, p, p, p, p, p],
     "fmd_vq_codebook_grad": [p, i32, i32, i32, i32, p, p, p, p, f32, p, p],
     "fmd_vq_backward": [p, i32, i32, i32, i32, p, p, p, i32, p, f32, f32, p, i32, p],
+    "fmd_vq_join_bwd": [p, i32, i32, i32, i32, p, p, p, i32, i32, p, f32, f32, p, i32, p],
     "fmd_image_metrics_workspace": [i32, i32, i32, i32, i32],
     "fmd_image_metrics": [p, p, i32, i32, i32, i32, i32, i32, p, p, p, p, p],
     "fmd_vae_loss_workspace": [i32, i32, i32, i64, i32],

@@ -2,7 +2,8 @@
 ``encode`` runs the encoder with ``quant_conv`` folded into its output conv, ``decode`` runs
 ``post_quant_conv`` and the decoder, and ``forward`` chains encoder -> HIP quantizer (``csrc/vq.hip``) ->
 decoder on the fused engine (``fmdiff.runtime.vae_engine``) with the quantized latent handed over as the NHWC
-bf16 operand the decoder reads, so there is no channels-first round trip.
+bf16 operand the decoder reads, so there is no channels-first round trip.  ``forward_train`` is the same chain under
+a tape, connected to the parameters by autograd (training; ``forward`` itself carries no gradient).
 
 ``quantizer_type``: ``"classic"`` / ``"vq"`` (codebook parameter) or ``"ema"`` (codebook buffers);
 ``discriminator_type`` is kept for the configs, the discriminators themselves are VAE training."""
@@ -83,3 +84,13 @@ class VQVAE(BaseVAE):
     def forward(self, x: torch.Tensor):
         rec, q = self._engine().vq_forward(x)
         return rec, {"vq_loss": q.vq_loss, "perplexity": q.perplexity, "codes": q.codes}
+
+    def forward_train(self, x: torch.Tensor):
+        """``forward`` for training: the same tuple, with ``rec`` and ``vq_loss`` connected to the parameters by
+        autograd (``fmdiff.runtime.vae_engine.vqvae_forward_train``; perplexity and codes carry no gradient).  A
+        training-mode EMA codebook is updated by this call, as the reference's forward does; the classic codebook
+        parameter gets no gradient, as in the reference."""
+        from ...runtime.vae_engine import vqvae_forward_train
+        self._engine()
+        rec, vq_loss, perplexity, codes = vqvae_forward_train(self, x)
+        return rec, {"vq_loss": vq_loss, "perplexity": perplexity, "codes": codes}

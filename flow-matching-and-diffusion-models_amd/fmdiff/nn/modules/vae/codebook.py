@@ -21,24 +21,33 @@ import torch.nn as nn
 __all__ = ["VectorQuantizer", "VectorQuantizerEMA"]
 
 
+def _quantize_and_update(mod, zd, e, update, Cpad):
+    """The training-mode quantisation of the detached rows ``zd`` against ``e`` (the codebook object itself: the
+    plane cache is keyed on it) and, with ``update``, the EMA update.  Returns ``(ops.VQOut, saved)``: ``saved`` is
+    what the latent gradient reads, ``(z - q,)`` when the codebook has been rewritten (all the backward reads of
+    it), else ``(z, codes, codebook, hist)``.  One body for ``_QuantizeTrain`` and the engine's VQVAE walk."""
+    from ....runtime import ops
+    D = mod.embedding_dim
+    out = ops.vq_quantize(zd, D, e, mod.commitment_cost, mod.classic, eps=mod._stats_eps(), Cpad=Cpad)
+    if update:
+        saved = (ops.vq_residual(zd, D, out.codes, e),)
+        ops.vq_ema_update(zd, D, out.codes, out.hist, e, mod.ema_cluster_size, mod.ema_w, mod.decay, mod.eps)
+    else:
+        saved = (zd, out.codes, e, out.hist)
+    return out, saved
+
+
 class _QuantizeTrain(torch.autograd.Function):
     """(z_q channels-first, vq_loss) of channels-last rows ``z_nhwc``; ``embedding`` is an input only for the
     opt-in codebook gradient.  What backward needs is saved before ``update`` overwrites the codebook."""
 
     @staticmethod
     def forward(ctx, z_nhwc, embedding, mod, update, codebook_grad, Cpad):
-        from ....runtime import ops
         D = mod.embedding_dim
-        zd, e = z_nhwc.detach(), embedding   # the codebook object itself: the plane cache is keyed on it
-        out = ops.vq_quantize(zd, D, e, mod.commitment_cost, mod.classic, eps=mod._stats_eps(), Cpad=Cpad)
+        out, saved = _quantize_and_update(mod, z_nhwc.detach(), embedding, update, Cpad)
         ctx.D, ctx.codebook_grad = D, codebook_grad
-        ctx.c = mod.commitment_cost - 1.0 if mod.classic else mod.commitment_cost
-        if update:
-            # the codebook is rewritten below: keep z - q, which is all the backward reads of it
-            ctx.save_for_backward(ops.vq_residual(zd, D, out.codes, e))
-            ops.vq_ema_update(zd, D, out.codes, out.hist, e, mod.ema_cluster_size, mod.ema_w, mod.decay, mod.eps)
-        else:
-            ctx.save_for_backward(zd, out.codes, e, out.hist)
+        ctx.c = mod._latent_coef()
+        ctx.save_for_backward(*saved)
         ctx.update = update
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(out.codes, out.perplexity, out.zq_nhwc, out.hist, out.mse)
@@ -89,6 +98,20 @@ class _VectorQuantizerBase(nn.Module):
 
     def _updates(self) -> bool:
         return False
+
+    def _latent_coef(self) -> float:
+        """``c`` of the latent gradient ``g_loss c 2/(MD) (z - q)``: beta, or beta - 1 for the classic quantizer."""
+        return self.commitment_cost - 1.0 if self.classic else self.commitment_cost
+
+    def quantize_train_saved(self, z_nhwc: torch.Tensor, Cpad=None):
+        """``quantize_train_nhwc`` without the autograd node, for a caller that runs the backward itself (the
+        engine's VQVAE walk, whose latent gradient goes through ``ops.vq_join_bwd``): the same quantisation and,
+        in training mode, the same EMA update.  Returns ``(ops.VQOut, saved)`` with ``saved`` as
+        ``_quantize_and_update`` describes it; nothing carries a gradient."""
+        from ....runtime import ops
+        ops._need_cuda(z_nhwc, type(self).__name__)
+        with torch.no_grad():
+            return _quantize_and_update(self, z_nhwc.detach(), self.embedding, self._updates(), Cpad)
 
     def quantize_train_nhwc(self, z_nhwc: torch.Tensor, codebook_grad: bool = False, Cpad=None):
         """The engine's training entry: ``z_nhwc`` fp32 channels-last ``[N, *spatial, >= embedding_dim]``.  Returns

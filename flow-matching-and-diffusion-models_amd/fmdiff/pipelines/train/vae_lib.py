@@ -1,6 +1,6 @@
 """VAE trainer pieces (reference ``src/pipelines/train/vae_lib.py``): the scheduler factory, the discriminator
 gate and the training criterion as one object over the HIP loss kernels (``fmdiff.nn.losses.vae``,
-``csrc/vae_loss.hip``), and one whole AutoencoderKL optimizer step on the engine (``VAETrainStep``).  The trainer
+``csrc/vae_loss.hip``), and one whole AutoencoderKL or VQVAE optimizer step on the engine (``VAETrainStep``).  The trainer
 loop itself is not built: the datasets, checkpoints and images around the step, the discriminator and the
 perceptual loss are missing."""
 from __future__ import annotations
@@ -125,7 +125,7 @@ class VAECriterion:
 
 
 class VAETrainStep:
-    """One optimizer step of AutoencoderKL on the engine, the body of the reference's loop
+    """One optimizer step of AutoencoderKL or VQVAE on the engine, the body of the reference's loop
     (``vae_lib.py:198-316``) without AMP, microbatching, discriminator or perceptual terms::
 
         inputs = model.image_to_model_range(raw_images)
@@ -133,6 +133,14 @@ class VAETrainStep:
         out = VAECriterion(...)(rec, raw_images, kl=kl, global_step=global_step)
         out["loss"].backward()
         AdamW(lr, weight_decay)                      # torch defaults otherwise, as the reference builds it
+
+    A model with a codebook takes the VQ path: ``rec, aux = model.forward_train(inputs)`` and
+    ``criterion(rec, raw_images, vq_loss=aux["vq_loss"], global_step=global_step)``; it has no posterior noise
+    (``eps`` raises).  The EMA codebook's buffers are updated by that forward, as in the reference, and are not
+    optimizer state.  The classic ``codebook.embedding`` is a Parameter that receives no gradient in the
+    reference, so torch's AdamW skips it, weight decay included: here it is kept out of the flat update (it is
+    laid out behind the trained parameters and the AdamW launch stops short of it), so it stays bit-identical for
+    any ``weight_decay``.
 
     Parameters, gradients and Adam moments are flat fp32 buffers (``FlatParams``), the optimizer is one
     ``ops.adamw`` launch, and because it writes the parameters through raw pointers the step then re-derives the
@@ -148,16 +156,21 @@ class VAETrainStep:
         if self.criterion.gan_weight > 0:
             raise NotImplementedError("GAN discriminators (VAE training) are outside the fmdiff hot path; set "
                                       "gan_weight to 0")
-        if self.criterion.effective_codebook_weight != 0.0 or hasattr(model, "codebook"):
-            raise NotImplementedError("VAETrainStep trains AutoencoderKL; the VQVAE trunk backward is not built "
-                                      "(DESIGN.md section 7)")
+        self.vq = hasattr(model, "codebook")
+        if self.criterion.effective_codebook_weight != 0.0 and not self.vq:
+            raise NotImplementedError("VAETrainStep: a codebook weight needs a model with a codebook (VQVAE); "
+                                      "AutoencoderKL trains with latent_type / reg_type 'kl'")
         self.model = model
         self.eng = get_vae_engine(model)
         self.eng.check_trainable()
         self.lr = float(training_cfg.get("learning_rate", 1e-4) if lr is None else lr)
         self.weight_decay = float(training_cfg.get("weight_decay", 0.0) if weight_decay is None else weight_decay)
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
-        self.flat = FlatParams(model)
+        # parameters that get no gradient in the reference (the classic codebook) behind the trained ones
+        frozen = [p for p in model.codebook.parameters()] if self.vq else []
+        ids = {id(p) for p in frozen}
+        self.flat = FlatParams(model, first=[p for p in model.parameters() if id(p) not in ids] if frozen else None)
+        self.n_trained = self.flat.split_at if frozen else self.flat.numel
         self.m = torch.zeros_like(self.flat.data)
         self.v = torch.zeros_like(self.flat.data)
         self.global_step = 0
@@ -165,17 +178,24 @@ class VAETrainStep:
 
     def step(self, raw_images: torch.Tensor, eps: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """``raw_images``: the batch in [0, 1], NCHW fp32 on the device; ``eps``: the posterior noise (None: drawn
-        on the device).  Returns VAECriterion's totals as device scalars (``loss`` detached)."""
+        on the device; a VQVAE takes none).  Returns VAECriterion's totals as device scalars (``loss`` detached)."""
+        if self.vq and eps is not None:
+            raise ValueError("VAETrainStep.step: eps is the AutoencoderKL posterior noise; a VQVAE has none")
         self.flat.grad.zero_()
         inputs = self.model.image_to_model_range(raw_images)
-        rec, _, kl = self.model.forward_train(inputs, eps, sample_posterior=True)
-        out = self.criterion(rec, raw_images, kl=kl, global_step=self.global_step)
+        if self.vq:
+            rec, aux = self.model.forward_train(inputs)
+            out = self.criterion(rec, raw_images, vq_loss=aux["vq_loss"], global_step=self.global_step)
+        else:
+            rec, _, kl = self.model.forward_train(inputs, eps, sample_posterior=True)
+            out = self.criterion(rec, raw_images, kl=kl, global_step=self.global_step)
         out["loss"].backward()
         out["loss"] = out["loss"].detach()
         self.global_step += 1
         from ...runtime import ops
-        ops.adamw(self.flat.data, self.flat.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
-                  self.weight_decay, self.global_step)
+        n = self.n_trained
+        ops.adamw(self.flat.data[:n], self.flat.grad[:n], self.m[:n], self.v[:n], self.lr, self.betas[0],
+                  self.betas[1], self.eps, self.weight_decay, self.global_step)
         self.eng.invalidate_weights()
         return out
 
@@ -224,6 +244,6 @@ class VAETrainStep:
 def train(dataset, json_path, val_dataset=None, resume=None) -> None:
     raise NotImplementedError("The VAE trainer loop is not built: the datasets, checkpoints and sample images "
                               "around the step, the discriminator and the perceptual loss are still missing "
-                              "(DESIGN.md section 7).  One AutoencoderKL optimizer step is VAETrainStep; the "
+                              "(DESIGN.md section 7).  One AutoencoderKL or VQVAE optimizer step is VAETrainStep; the "
                               "criterion it calls is VAECriterion; the quantizer half is "
                               "VectorQuantizer*.quantize_train.")

@@ -318,7 +318,8 @@ class WeightCache:
 
 
 class Ctx:
-    __slots__ = ("emb", "demb", "tape", "N", "eo_all", "demb_all", "mark", "cca", "marks", "drop_seeded")
+    __slots__ = ("emb", "demb", "tape", "N", "eo_all", "demb_all", "mark", "cca", "marks", "drop_seeded",
+                 "like_forward")
 
     def __init__(self, emb, save, N):
         self.emb = emb
@@ -331,6 +332,9 @@ class Ctx:
         self.marks: List[int] = []   # tape length before each encoder stage (backward segments, see seg_ranges)
         self.cca = None         # cross-attention context (context_ca), fp32 as passed to the model
         self.drop_seeded = False   # this forward has advanced the dropout seed counter
+        # a taped walk whose outputs must carry the bits of the forward-only walk (VQVAE.forward_train): the small
+        # levels run on the forward-only kernels and their tape entries recompute the layer (LayerEngine._replay)
+        self.like_forward = False
 
 
 def _check_conv(c: Conv, ks, stride, pad):
@@ -393,19 +397,40 @@ class LayerEngine:
         self.wc.invalidate()
 
     # ------------------------------------------------------------- layers
+    def _replay(self, ctx: Ctx, o: Act, layer) -> Act:
+        """``o``: the output of a layer that ran on a forward-only kernel, which keeps nothing for a backward.
+        Without a tape that is all.  Under a ``like_forward`` tape the entry recomputes the layer on the taped
+        route (``layer(ctx)``, the same input Acts, so their gradients land where they always do) and runs that
+        tape with ``o``'s gradient: activation recomputation, at the small levels only, so that the walk's outputs
+        are the forward-only walk's bit for bit.  The recomputed intermediates differ from the forward's by bf16
+        rounding noise, as any two routes of this engine do."""
+        if ctx.tape is None:
+            return o
+
+        def bwd():
+            sub = Ctx(ctx.emb, False, ctx.N)
+            sub.tape, sub.eo_all, sub.cca = [], ctx.eo_all, ctx.cca
+            o2 = layer(sub)
+            o2.grad = o.grad
+            for fn in reversed(sub.tape):
+                fn()
+        ctx.tape.append(bwd)
+        return o
+
     def conv_layer(self, conv: Conv, x: Act, ctx: Ctx, *, stride=1, upsample=False, cpad=None):
         """Plain 3x3 conv (input conv, DownsampleND, UpsampleND)."""
         _check_conv(conv, 3, stride, 1)
         Cin = x.C
         N_, sp = x.t.shape[0], tuple(x.t.shape[1:-1])
-        if (ctx.tape is None and len(sp) == 2 and not self.dims1 and conv.weight.dim() == 4 and
+        if ((ctx.tape is None or ctx.like_forward) and len(sp) == 2 and not self.dims1 and conv.weight.dim() == 4 and
                 conv.weight.shape[1] == Cin):
             # forward only, small level: one launch with the output statistics (fmd_conv_small)
             mode = "s2" if stride == 2 else "up" if upsample else "s1"
             if ops.conv_small_ok(tuple(x.t.shape), conv.out_channels, mode=mode):
                 out, st = ops.conv_small(x.t, conv.out_channels, self.wc.get(conv.weight, 0), mode=mode,
                                          bias=conv.bias)
-                return Act(out, st)
+                return self._replay(ctx, Act(out, st), lambda c: self.conv_layer(conv, x, c, stride=stride,
+                                                                                 upsample=upsample, cpad=cpad))
         exact = conv.weight.shape[1] == Cin
         route = route3x3(N_, sp, conv.out_channels, Cin, stride=stride, upsample=upsample, exact_weight=exact)
         if route == "s2d":   # DownsampleND's conv on the space-to-depth halo kernel (3-D: depth taps as chunks)
@@ -604,10 +629,10 @@ class LayerEngine:
             es = eo.shape[1]
         else:   # the embedding projection feeds nothing (or the block has none: VAE ResBlocks)
             eo, es = None, 0
-        if ctx.tape is None and not drop and len(sp) == 2 and not self.dims1:
+        if (ctx.tape is None or ctx.like_forward) and not drop and len(sp) == 2 and not self.dims1:
             o = self._res_block_small(m, x0, x1, eo, es, ss, add)
             if o is not None:
-                return o
+                return self._replay(ctx, o, lambda c: self.res_block(m, xs, c))
         halo1 = route3x3(N, sp, Cout, Cin, pro=True) == "halo"
         mat1 = _materialise(halo1, x1, Cin, HW, len(sp) == 3)
         if mat1 and not halo1:   # without the fused prologue the halo kernel's affine-table limit is moot
@@ -850,7 +875,7 @@ class LayerEngine:
             lin = None
         else:
             raise NotImplementedError(type(m).__name__)
-        if ctx.tape is None and len(sp) == 2 and SMALL_ATTN:
+        if (ctx.tape is None or ctx.like_forward) and len(sp) == 2 and SMALL_ATTN:
             # forward only, small level: the GroupNorm folded into the qkv projection and the output projection with
             # its residual and statistics, one fmd_conv_small launch each (no gn_prep, split-K combine or
             # channel_stats launches)
@@ -868,7 +893,7 @@ class LayerEngine:
                     o, _ = ops.attention_fwd(qkv, T, heads, dh, raw)
                 out, st = ops.conv_small(o.view(N, H, W, inner), Cc, self.wc.get(wo, 0), mode="point", bias=bo,
                                          resid=x4)
-                return Act(out.view(x.t.shape), st)
+                return self._replay(ctx, Act(out.view(x.t.shape), st), lambda c: self.attention(m, x, c))
         a, b, mr = ops.gn_prep(_stats(x), None, N, T, Cc, 0, norm.num_groups, norm.eps, norm.weight, norm.bias)
         qkv, _ = ops.conv(x4, 3 * inner, self.wc.get(wq, 0), ks=1, pad=0, pro=(a, b, False), bias=bq)
         if lin is not None:

@@ -1691,6 +1691,60 @@ def vq_backward(z_flat, D: int, codes, codebook, g_zq, g_loss, c: float, *, out=
     return dz
 
 
+def vq_join_bwd(g_zq, D: int, z_flat, codes, codebook, g_loss, c: float, *, ld_out: Optional[int] = None,
+                out=None) -> torch.Tensor:
+    """The latent join of the VQVAE backward in one launch: ``vq_backward``'s value
+    ``g_zq + g_loss * c * (2 / (M D)) * (z - q)``, element for element, rounded once (to nearest even) to the bf16
+    channels-last operand ``[N, *spatial, ld_out]`` of the encoder head's backward; channels ``D .. ld_out - 1`` are
+    exact zeros (default ``ld_out``: D rounded up to 8).
+
+    ``g_zq``: the 1x1 data gradient as the conv left it, bf16 or fp32 channels-last ``[N, *spatial, >= D]`` with a
+    row stride that is a multiple of 8, or None (zero).  ``z_flat`` / ``codes`` / ``codebook`` as for
+    ``vq_backward`` (``codebook`` None: ``z_flat`` holds the saved residual z - q).  ``g_loss``: a one-element fp32
+    device tensor or None (zero).  Padding channels of the inputs are never read.  Nothing synchronises."""
+    what = "vq_join_bwd"
+    M, ldz = _vq_rows(z_flat, D, what)
+    dev = z_flat.device
+    if not 1 <= D <= 256:
+        raise ValueError(f"{what}: 1 <= D <= 256, got {D}")
+    K = 1
+    if codebook is not None:
+        K = codebook.shape[0]
+        _vq_state(codebook, (K, D), what)
+        _need_cuda(codes, what)
+        if codes.dtype != torch.int64 or not codes.is_contiguous() or codes.numel() != M:
+            raise RuntimeError(f"{what}: codes must be contiguous int64 with {M} elements")
+    ldg, g_f32 = 0, 0
+    if g_zq is not None:
+        _need_cuda(g_zq, what)
+        if g_zq.dtype not in (BF16, F32) or not g_zq.is_contiguous() or g_zq.dim() < 2:
+            raise RuntimeError(f"{what}: g_zq must be contiguous bf16 or fp32 rows, got {g_zq.dtype} "
+                               f"{tuple(g_zq.shape)}")
+        ldg, g_f32 = int(g_zq.shape[-1]), int(g_zq.dtype == F32)
+        if ldg < D or ldg % 8 or g_zq.numel() // ldg != M or g_zq.data_ptr() % 16:
+            raise ValueError(f"{what}: g_zq needs {M} 16-byte aligned rows with a stride >= {D} that is a multiple "
+                             f"of 8, got {tuple(g_zq.shape)}")
+    if g_loss is not None:
+        _need_cuda(g_loss, what)
+        if g_loss.dtype != F32 or g_loss.numel() != 1:
+            raise RuntimeError(f"{what}: g_loss must be one fp32 element")
+    if out is None:
+        ld_out = int(ld_out or max(8, -(-D // 8) * 8))
+        if ld_out < D or ld_out % 8:
+            raise ValueError(f"{what}: ld_out {ld_out} must be a multiple of 8 and >= {D}")
+        out = torch.empty((*z_flat.shape[:-1], ld_out), device=dev, dtype=BF16)
+    else:
+        _need_cuda(out, what)
+        ld_out = int(out.shape[-1])
+        if (out.dtype != BF16 or not out.is_contiguous() or ld_out < D or ld_out % 8 or out.numel() // ld_out != M
+                or out.data_ptr() % 16):
+            raise ValueError(f"{what}: out must be contiguous bf16 with {M} rows and a stride >= {D} that is a "
+                             f"multiple of 8, got {out.dtype} {tuple(out.shape)}")
+    _lib.call("fmd_vq_join_bwd", _p(z_flat), ldz, M, K, D, _p(codes) if codebook is not None else None, _p(codebook),
+              _p(g_zq), g_f32, ldg, _p(g_loss), float(c), float(2.0 / (M * D)), _p(out), ld_out, stream())
+    return out
+
+
 def vq_residual(z_flat, D: int, codes, codebook) -> torch.Tensor:
     """``z - codebook[codes]`` rounded once (padding channels zero): what ``vq_backward`` needs of a codebook that
     is about to be overwritten by ``vq_ema_update``.  ``fma(1, z - q, 0)`` is exact, so a later

@@ -13,8 +13,14 @@ folded into conv_out's weights, so ``encode`` ends in one head launch; ``post_qu
 AutoencoderKL also trains here (2-D, eager): ``train_encode`` / ``train_decode`` walk the same trunks under a
 tape, their backwards run it the way ``UNetEngine.backward`` does, the gradient of the folded conv is unfolded
 exactly onto conv_out and quant_conv (``unfold_quant_grads``), and post_quant_conv's backward is one VALU launch
-(``ops.pointwise_bwd``, csrc/pointwise_bwd.hip).  ``vae_forward_train`` ties them to autograd.  The VQVAE trunk
-backward is not built.
+(``ops.pointwise_bwd``, csrc/pointwise_bwd.hip).  ``vae_forward_train`` ties them to autograd.
+
+VQVAE trains on the same walks (``vq_train_forward`` / ``vq_train_backward``, one autograd node,
+``vqvae_forward_train``).  Its latent convs are up to 256 channels wide, so post_quant_conv's backward runs on the
+MFMA weight-gradient and 1x1 conv kernels, and the quantizer's gradient joins the 1x1's fp32 data gradient in one
+launch that writes the encoder head's bf16 operand (``ops.vq_join_bwd``, csrc/vq_train.hip).
+Its trunks walk ``like_forward``: the small levels run on the forward-only kernels ``vq_forward`` uses and are
+recomputed in the backward (``LayerEngine._replay``), so ``forward_train`` carries ``forward``'s bits.
 """
 from __future__ import annotations
 
@@ -34,13 +40,14 @@ class VAEEngine(LayerEngine):
         self._fold = None       # conv_out with quant_conv folded in (_folded_out)
         self._fold_key = None
 
-    def _ctx(self, part, N, dev, save=False):
+    def _ctx(self, part, N, dev, save=False, like_forward=False):
         emb = None
         if part.emb_channels is not None:   # the reference feeds zeros (encoder.py:141-144)
             emb = torch.zeros((N, part.emb_channels), device=dev, dtype=F32)
         ctx = Ctx(emb, False, N)
         if save:   # training walks have no embedding (check_trainable): a tape, no demb
             ctx.tape = []
+            ctx.like_forward = like_forward
         return ctx
 
     def _stage(self, x):
@@ -55,10 +62,10 @@ class VAEEngine(LayerEngine):
             h = self.attention(part.mid_attn, h, ctx)
         return self.res_block(part.mid_block2, [h], ctx)
 
-    def _encoder_trunk(self, enc, x, save=False):
+    def _encoder_trunk(self, enc, x, save=False, like_forward=False):
         if enc.spatial_dims != 2:
             raise NotImplementedError("fmdiff VAE engine: spatial_dims=2")
-        ctx = self._ctx(enc, x.shape[0], x.device, save)
+        ctx = self._ctx(enc, x.shape[0], x.device, save, like_forward)
         h = self.conv_layer(enc.conv_in.conv, Act(self._stage(x), need_grad=False), ctx)
         for stage in enc.downs:
             for i, blk in enumerate(stage.blocks):
@@ -171,13 +178,13 @@ class VAEEngine(LayerEngine):
         return self._decode_staged(zs), z, kl
 
 
-    # ------------------------------------------------------------ training (AutoencoderKL, 2-D, eager)
+    # ------------------------------------------------------------ training (2-D, eager; AutoencoderKL first)
     def check_trainable(self):
         """Refuse what the trunk backward is not built (or not checked) for."""
         vae = self.m
         what = "fmdiff VAE training"
-        if not hasattr(vae, "quant_conv") or hasattr(vae, "codebook"):
-            raise NotImplementedError(f"{what}: AutoencoderKL only (the VQVAE trunk backward is not built, DESIGN.md 7)")
+        if not hasattr(vae, "quant_conv"):
+            raise NotImplementedError(f"{what}: AutoencoderKL and VQVAE only")
         enc, dec, pq = vae.encoder, vae.decoder, vae.post_quant_conv.conv
         if enc.spatial_dims != 2 or dec.spatial_dims != 2:
             raise NotImplementedError(f"{what}: spatial_dims=2")
@@ -187,7 +194,11 @@ class VAEEngine(LayerEngine):
             raise NotImplementedError(f"{what}: emb_channels (no reference path to check the embedding against)")
         if any(isinstance(mod, ResBlockND) and float(mod.dropout or 0.0) > 0 for mod in vae.modules()):
             raise NotImplementedError(f"{what}: dropout > 0")
-        if max(pq.in_channels, pq.out_channels) > ops.POINTWISE_MAXC:
+        if hasattr(vae, "codebook"):   # the latent convs on the MFMA routes: the quantizer's own limit
+            if pq.in_channels > VQ_MAX_EMBED:
+                raise NotImplementedError(f"{what}: embed_dim up to {VQ_MAX_EMBED} (the quantizer kernels), got "
+                                          f"{pq.in_channels}")
+        elif max(pq.in_channels, pq.out_channels) > ops.POINTWISE_MAXC:
             raise NotImplementedError(f"{what}: z_channels and embed_dim up to {ops.POINTWISE_MAXC} (the latent 1x1 "
                                       f"backward kernel), got {pq.out_channels} and {pq.in_channels}")
 
@@ -220,12 +231,14 @@ class VAEEngine(LayerEngine):
             ops.gb_flush()
         self._join()
 
-    def train_encode(self, x):
-        """Encoder + folded quant_conv under a tape: (fp32 NHWC moments [N, h, w, Kp], state for the backward)."""
+    def train_encode(self, x, like_forward=False):
+        """Encoder + folded quant_conv under a tape: (fp32 NHWC moments [N, h, w, Kp], state for the backward).
+        ``like_forward``: the small levels on the forward-only kernels, their backward recomputed
+        (``LayerEngine._replay``), so that the moments are ``_encode_nhwc``'s bit for bit."""
         self.check_trainable()
         vae = self.m
         enc = vae.encoder
-        h, ctx = self._encoder_trunk(enc, x, save=True)
+        h, ctx = self._encoder_trunk(enc, x, save=True, like_forward=like_forward)
         fold = self._folded_out(vae)
         mom = self.head(enc.norm_out, fold, h, ctx)
         head_bwd, self._head_bwd = self._head_bwd, None   # one slot: the decoder's head would overwrite it
@@ -252,15 +265,16 @@ class VAEEngine(LayerEngine):
         fold.weight.grad.zero_()
         fold.bias.grad.zero_()
 
-    def train_decode(self, zs):
-        """post_quant_conv + decoder under a tape from the staged latent: (fp32 NHWC output, state)."""
+    def train_decode(self, zs, like_forward=False):
+        """post_quant_conv + decoder under a tape from the staged latent: (fp32 NHWC output, state).
+        ``like_forward``: as in ``train_encode``; the output is ``_decode_staged``'s bit for bit."""
         self.check_trainable()
         vae = self.m
         dec, pq = vae.decoder, vae.post_quant_conv.conv
         Kp = max(CPAD, -(-pq.out_channels // 8) * 8)
         hz, _ = ops.conv(zs, Kp, self.wc.get(pq.weight, 0, Kp, zs.shape[-1]), ks=1, pad=0,
                          bias=self.wc.padded(pq.bias, Kp))
-        ctx = self._ctx(dec, zs.shape[0], zs.device, save=True)
+        ctx = self._ctx(dec, zs.shape[0], zs.device, save=True, like_forward=like_forward)
         hin = Act(hz, need_grad=True)
         out = self._decoder_trunk(dec, hin, ctx)
         head_bwd, self._head_bwd = self._head_bwd, None
@@ -276,6 +290,50 @@ class VAEEngine(LayerEngine):
         g_z, _, _ = ops.pointwise_bwd(hin.grad, zs, pq.weight.detach().reshape(pq.out_channels, pq.in_channels),
                                       dW=pq.weight.grad, db=pq.bias.grad, accumulate=True)
         return g_z
+
+    # ------------------------------------------------------------ training (VQVAE, 2-D, eager)
+    def vq_train_forward(self, x):
+        """``vq_forward`` under a tape: encoder trunk, head with the folded quant_conv, the quantizer's training
+        call (a training-mode EMA codebook has been updated when this returns), post_quant_conv as the MFMA 1x1 on
+        the staged z_q, decoder trunk.  Both trunks walk ``like_forward``: in eval mode, and for the classic quantizer,
+        rec, vq_loss, perplexity and codes are ``vq_forward``'s bit for bit.  Returns (fp32 NHWC decoder output, ops.VQOut, state for the backward)."""
+        self.check_trainable()
+        vae = self.m
+        quant_in, enc_state = self.train_encode(x, like_forward=True)
+        D = vae.codebook.embedding_dim
+        q, saved = vae.codebook.quantize_train_saved(quant_in, Cpad=max(CPAD, -(-D // 8) * 8))
+        out, dec_state = self.train_decode(q.zq_nhwc, like_forward=True)
+        return out, q, (enc_state, dec_state, saved, vae.codebook._latent_coef(), D, quant_in.shape[-1])
+
+    def vq_train_backward(self, state, dpred, g_loss):
+        """``dpred``: bf16 NHWC gradient of the decoder output; ``g_loss``: one-element fp32 device tensor, the
+        gradient of vq_loss (None: zero).  Decoder tape, then post_quant_conv's backward on the MFMA routes (the
+        1x1 weight gradient and the transposed 1x1 as data gradient, stored fp32), then the latent join
+        (``ops.vq_join_bwd``) straight into the bf16 operand of the encoder head's backward, then the encoder tape
+        and the unfold.  Between the data gradient and the head's backward there is the join kernel and nothing
+        else.  Accumulates into ``.grad`` of every trunk parameter; the codebook gets none (as in the reference)."""
+        enc_state, (dctx, dec_head_bwd, hin, zs), saved, c, D, Kp = state
+        pq = self.m.post_quant_conv.conv
+        Z, Zp, Dp = pq.out_channels, hin.t.shape[-1], zs.shape[-1]
+        self._run_backward(dec_head_bwd, dpred, dctx.tape)
+        dctx.tape = None
+        dy = hin.grad   # bf16 [N, h, w, Zp], padding channels zero (conv_in's padded weight rows are zero)
+        if Zp == Z and Dp == D:
+            ops.wgrad(zs, dy, pq.weight.grad, ks=1, pad=0, db=pq.bias.grad, immediate=True)
+        else:   # padded channels: through zeroed fp32 temporaries cut to size, as the head's own weight gradient
+            tmpw = torch.zeros((Zp, Dp, 1, 1), device=dy.device, dtype=F32)
+            tmpb = torch.zeros((Zp,), device=dy.device, dtype=F32)
+            ops.wgrad(zs, dy, tmpw, ks=1, pad=0, db=tmpb, accumulate=False, immediate=True)
+            pq.weight.grad.add_(tmpw[:Z, :D])
+            pq.bias.grad.add_(tmpb[:Z])
+        g, _ = ops.conv(dy, Dp, self.wc.get(pq.weight, 1, Zp, Dp), ks=1, pad=0, transposed=True,
+                        out_hw_=tuple(dy.shape[1:-1]), out_f32=True)
+        if len(saved) == 1:   # the EMA update has overwritten the codebook: the saved residual z - q
+            dz = ops.vq_join_bwd(g, D, saved[0], None, None, g_loss, c, ld_out=Kp)
+        else:
+            z, codes, e, _ = saved
+            dz = ops.vq_join_bwd(g, D, z, codes, e, g_loss, c, ld_out=Kp)
+        self.train_encode_backward(enc_state, dz)
 
 
 def unfold_quant_grads(wq, w_out, b_out, dwf, dbf):
@@ -338,6 +396,41 @@ def vae_forward_train(module, x, eps=None, sample_posterior=True):
                                   staged_channels=max(CPAD, -(-E // 8) * 8))
     rec = _VAEDecodeFunction.apply(z, zs, eng, *params)
     return rec, z, kl
+
+
+class _VQVAETrainFunction(torch.autograd.Function):
+    """x -> (rec NCHW fp32, vq_loss, perplexity, codes): the whole VQVAE training forward as one node, so that the
+    latent gradient stays the engine's own bf16 channels-last tensor from the 1x1's data gradient to the encoder
+    head (autograd would cast the gradient of an fp32 latent to fp32).  Parameter gradients are written into
+    ``.grad``; perplexity and codes carry none."""
+
+    @staticmethod
+    def forward(fctx, x, engine, *params):
+        out, q, state = engine.vq_train_forward(x)
+        fctx.engine, fctx.state, fctx.kpad = engine, state, out.shape[-1]
+        fctx.mark_non_differentiable(q.perplexity, q.codes)
+        return ops.nhwc_to_nchw(out, engine.m.decoder.conv_out.conv.out_channels), q.vq_loss, q.perplexity, q.codes
+
+    @staticmethod
+    def backward(fctx, grec, gloss, *_):
+        eng = fctx.engine
+        eng.ensure_grads()
+        eng.vq_train_backward(fctx.state, ops.nchw_to_nhwc(grec.contiguous(), fctx.kpad),
+                              gloss.float().reshape(1))
+        fctx.state = None
+        return (None, None) + tuple(None for _ in eng.m.parameters())
+
+
+def vqvae_forward_train(module, x):
+    """VQVAE.forward_train: (rec NCHW fp32, vq_loss, perplexity, codes); ``rec`` and ``vq_loss`` are connected to
+    the parameters by autograd."""
+    eng = get_vae_engine(module)
+    eng.check_trainable()
+    ops._need_cuda(x, f"{type(module).__name__}.forward_train")
+    return _VQVAETrainFunction.apply(x, eng, *module.parameters())
+
+
+VQ_MAX_EMBED = 256   # widest code the quantizer kernels take (csrc/vq.hip, csrc/vq_train.hip)
 
 
 def get_vae_engine(module) -> VAEEngine:

@@ -707,6 +707,15 @@ int fmd_vq_codebook_grad(const float* z, int32_t ldz, int32_t M, int32_t K, int3
 int fmd_vq_backward(const float* z, int32_t ldz, int32_t M, int32_t K, int32_t D, const int64_t* codes,
                     const float* embedding, const float* g_zq, int32_t ldg, const float* g_loss, float c,
                     float scale, float* dz, int32_t lddz, fmd_stream_t s);
+/* The latent join of the VQVAE backward: fmd_vq_backward's value, element for element and in its operation order,
+ * with g_zq read as the 1x1 data gradient left it (channels-last, g_f32 = 0: bf16, 1: fp32; null: zero) and dz
+ * stored as bf16 (one rounding, to nearest even): the channels-last operand of the encoder head's backward, with
+ * channels D .. lddz-1 exact zeros.  g_loss null: zero.  Channels >= D of z, g_zq and embedding rows are never
+ * read.  1 <= D <= 256; ldg and lddz multiples of 8 and >= D, g_zq and dz 16-byte aligned; ldz >= D.  Returns -1
+ * on anything else; one launch, no workspace. */
+int fmd_vq_join_bwd(const float* z, int32_t ldz, int32_t M, int32_t K, int32_t D, const int64_t* codes,
+                    const float* embedding, const void* g_zq, int32_t g_f32, int32_t ldg, const float* g_loss,
+                    float c, float scale, void* dz, int32_t lddz, fmd_stream_t s);
 
 /* ------------------------------------------------------------- image metrics
  * Per-image MSE, PSNR and SSIM of the evaluate modes (src/pipelines/samplers/diffusion_like.py:251-263,

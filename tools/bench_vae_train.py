@@ -1,9 +1,14 @@
 """Time one AutoencoderKL optimizer step on the engine (``VAETrainStep.step``) for the model block of the reference's
 ``configs/LDCT/LDCT_autoencoder_kl.json`` (82.6 M parameters, 256x256, batch 4, synthetic input, the config's own
 training block: l1, kl_weight 1e-6, no GAN, no perceptual term), with ``VAEEngine.kl_forward`` on the same model as
-the yardstick.
+the yardstick; the same for the VQVAE of ``configs/LDCT/LDCT_vqvae.json`` (EMA codebook) and
+``LDCT_vqvae_original.json`` (classic codebook) with ``VAEEngine.vq_forward`` as the yardstick (``--arm vq_ema`` /
+``vq_classic``); and an A/B of the latent-join kernel against the four-pass composition it replaces at
+M = 4 x 32 x 32 rows, D = 256 (``--arm join``; eager calls at this size measure the host's launch rate, ``--graph``
+replays a captured graph of 50 calls of each arm and measures the device).
 
-    python tools/bench_vae_train.py [--out profiles/vae_train_bench.jsonl] [--batch 4] [--steps 10] [--repeats 5]
+    python tools/bench_vae_train.py [--arm kl|vq_ema|vq_classic|join|all] [--out profiles/vae_train_bench.jsonl]
+                                    [--batch 4] [--steps 10] [--repeats 5]
 
 Protocol: 3 warm-up calls of each arm, then ``--repeats`` windows per arm, alternating, each ``--steps`` calls
 between two HIP events after a device synchronise.  One JSON line: the median, minimum and maximum ms per call of
@@ -29,6 +34,13 @@ LDCT_VAE = dict(in_channels=1, out_channels=1, resolution=256, base_ch=128, down
                 attn_dim_head=64)
 LDCT_TRAINING = {"learning_rate": 1e-4, "weight_decay": 0.0, "kl_weight": 1e-6, "kl_anneal_steps": 0, "reg_type": "kl",
                  "recon_type": "l1", "perceptual_weight": 0.0, "gan_weight": 0.0}
+LDCT_VQ = dict(in_channels=1, out_channels=1, resolution=256, base_ch=32, down_channels=[32, 64, 128, 256],
+               num_res_blocks=2, attn_resolutions=[], z_channels=256, embed_dim=256, dropout=0.0, use_attention=False,
+               spatial_dims=2, emb_channels=None, use_scale_shift_norm=False, attn_heads=1, attn_dim_head=64,
+               codebook_size=16384, vq_beta=0.25, vq_ema_decay=0.99, vq_ema_eps=1e-5)
+LDCT_VQ_TRAINING = {"learning_rate": 1e-4, "weight_decay": 0.0, "reg_type": "vq", "recon_type": "l1",
+                    "perceptual_weight": 0.0, "gan_weight": 0.0, "codebook_weight": 1.0}
+HBM_TBPS = 8.0   # MI355X HBM3E peak (MI355X_MICROARCH.md)
 FWD_GFLOP_PER_IMAGE = 269.2 + 618.7
 PEAK_BF16_TFLOPS = 2500.0   # MI355X dense bf16 MFMA
 
@@ -46,19 +58,161 @@ def _launches(fn):
         return None
 
 
+def _windows(arms, steps, repeats, warmup=3):
+    """ms per call of every arm: ``warmup`` calls each, then ``repeats`` windows per arm, alternating, each
+    ``steps`` calls between two HIP events after a device synchronise."""
+    import torch
+    for fn in arms.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in arms}
+    for _ in range(repeats):
+        for k, fn in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(steps):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / steps)
+    return ms
+
+
+def _stat(v):
+    return dict(median=statistics.median(v), min=min(v), max=max(v))
+
+
+def _emit(rec, out):
+    line = json.dumps(rec)
+    print(line)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "a") as f:
+            f.write(line + "\n")
+
+
+def bench_vq(a, qt):
+    """``VAETrainStep.step`` of the LDCT VQVAE against ``vq_forward`` (the same forward without a tape; for the EMA
+    codebook in eval mode, since the inference forward refuses a training-mode EMA quantizer)."""
+    import torch
+    from fmdiff.models.vae import VQVAE
+    from fmdiff.pipelines.train.vae_lib import VAETrainStep
+    from fmdiff.runtime.vae_engine import get_vae_engine
+    torch.manual_seed(0)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        vae = VQVAE(quantizer_type=qt, **LDCT_VQ).cuda().train()
+    g = torch.Generator(device="cuda").manual_seed(3)
+    img = torch.rand(a.batch, 1, 256, 256, device="cuda", generator=g)
+    step = VAETrainStep(vae, LDCT_VQ_TRAINING, {"latent_type": "vq"})
+    eng = get_vae_engine(vae)
+    xin = vae.image_to_model_range(img)
+
+    cb = vae.codebook
+
+    def forward():   # only the quantizer reads the flag (dropout is 0): one attribute, not a walk over the modules
+        cb.training = False
+        eng.vq_forward(xin)
+        cb.training = True
+
+    arms = {"step": lambda: step.step(img), "forward": forward}
+    ms = _windows(arms, a.steps, a.repeats)
+    out = step.step(img)
+    launches = {k: _launches(fn) for k, fn in arms.items()}
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    _emit(dict(workload=f"VQVAE (LDCT_vqvae{'_original' if qt == 'classic' else ''}, {qt} codebook) train step, "
+                        f"256x256, batch {a.batch}, eager",
+               params=sum(p.numel() for p in vae.parameters()), steps_per_window=a.steps, windows=a.repeats,
+               step_ms=_stat(ms["step"]), forward_ms=_stat(ms["forward"]),
+               step_to_forward=med["step"] / med["forward"], launches=launches, loss_after=float(out["loss"]),
+               vq_after=float(out["vq"]), global_step=step.global_step), a.out)
+
+
+def bench_join(a):
+    """``ops.vq_join_bwd`` (fp32 g, the engine's arm, and bf16 g) against the four passes it replaces on the bf16
+    data gradient: upcast to fp32, ``ops.vq_backward``, cast to bf16 (the 1x1 data gradient's own bf16 store is
+    common to both and not timed).  M = batch x 32 x 32 rows, D = 256, both residual modes."""
+    import torch
+    from fmdiff.runtime import ops
+    N, h, w, D, K = a.batch, 32, 32, 256, 16384
+    M = N * h * w
+    g = torch.Generator(device="cuda").manual_seed(5)
+    e = torch.randn((K, D), device="cuda", generator=g)
+    codes = torch.randint(0, K, (N, h, w), device="cuda", generator=g)
+    z = e[codes] + 0.3 * torch.randn((N, h, w, D), device="cuda", generator=g)
+    g32 = 0.1 * torch.randn((N, h, w, D), device="cuda", generator=g)
+    gbf = g32.to(torch.bfloat16)
+    gl = torch.full((1,), 0.37, device="cuda")
+    r = ops.vq_residual(z, D, codes, e)
+    dz32 = torch.empty_like(z)
+    out = torch.empty((N, h, w, D), device="cuda", dtype=torch.bfloat16)
+
+    def four(zz, cc, ee):
+        return lambda: ops.vq_backward(zz, D, cc, ee, gbf.float(), gl, 0.25, out=dz32).to(torch.bfloat16)
+
+    arms = {"join_f32_codebook": lambda: ops.vq_join_bwd(g32, D, z, codes, e, gl, 0.25, out=out),
+            "join_bf16_codebook": lambda: ops.vq_join_bwd(gbf, D, z, codes, e, gl, 0.25, out=out),
+            "four_pass_codebook": four(z, codes, e),
+            "join_f32_residual": lambda: ops.vq_join_bwd(g32, D, r, None, None, gl, 0.25, out=out),
+            "join_bf16_residual": lambda: ops.vq_join_bwd(gbf, D, r, None, None, gl, 0.25, out=out),
+            "four_pass_residual": four(r, None, None)}
+    assert torch.equal(arms["join_bf16_codebook"](), arms["four_pass_codebook"]())
+    per = 1
+    if a.graph:   # device time: 50 calls of an arm captured once and replayed, so the host's launch rate drops out
+        per = 50
+        graphs = {}
+        for k, fn in arms.items():
+            fn()
+            torch.cuda.synchronize()
+            graphs[k] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graphs[k]):
+                for _ in range(per):
+                    fn()
+        arms = {k: gr.replay for k, gr in graphs.items()}
+    ms = {k: [t / per for t in v] for k, v in _windows(arms, 50 * a.steps // per, a.repeats).items()}
+    # bytes a join moves per row: g (4 or 2 D) + z or the residual (4 D) [+ the code row (4 D) + the code (8)] + out (2 D)
+    by = {"join_f32_codebook": M * (4 * D + 4 * D + 4 * D + 8 + 2 * D), "join_bf16_codebook": M * (2 * D + 8 * D + 8 + 2 * D),
+          "join_f32_residual": M * (4 * D + 4 * D + 2 * D), "join_bf16_residual": M * (2 * D + 4 * D + 2 * D)}
+    rec = dict(workload=f"latent join, M = {M} rows, D = {D}, K = {K}" + (", graph replay" if a.graph else ", eager"),
+               calls_per_window=50 * a.steps, windows=a.repeats,
+               us={k: {kk: 1e3 * vv for kk, vv in _stat(v).items()} for k, v in ms.items()})
+    rec["tb_per_s"] = {k: by[k] / (1e-3 * statistics.median(ms[k])) / 1e12 for k in by}
+    rec["hbm_frac"] = {k: v / HBM_TBPS for k, v in rec["tb_per_s"].items()}
+    rec["four_pass_over_join"] = {m: statistics.median(ms[f"four_pass_{m}"]) / statistics.median(ms[f"join_bf16_{m}"])
+                                  for m in ("codebook", "residual")}
+    _emit(rec, a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--graph", action="store_true",
+                    help="join arm: time replays of a captured graph of 50 calls (device time) instead of eager calls")
+    ap.add_argument("--arm", default="kl", choices=("kl", "vq_ema", "vq_classic", "join", "all"))
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "bench_vae_train needs a ROCm GPU"
+    torch.cuda.set_stream(torch.cuda.Stream())
+    if a.arm in ("kl", "all"):
+        bench_kl(a)
+    if a.arm in ("vq_ema", "all"):
+        bench_vq(a, "ema")
+    if a.arm in ("vq_classic", "all"):
+        bench_vq(a, "classic")
+    if a.arm in ("join", "all"):
+        bench_join(a)
+
+
+def bench_kl(a):
+    import torch
     from fmdiff.models.vae import AutoencoderKL
     from fmdiff.pipelines.train.vae_lib import VAETrainStep
     from fmdiff.runtime.vae_engine import get_vae_engine
-    torch.cuda.set_stream(torch.cuda.Stream())
     torch.manual_seed(0)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -70,21 +224,7 @@ def main():
     eng = get_vae_engine(vae)
     xin = vae.image_to_model_range(img)
     arms = {"step": lambda: step.step(img, eps), "forward": lambda: eng.kl_forward(xin, eps)}
-    for fn in arms.values():
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in arms}
-    for _ in range(a.repeats):
-        for k, fn in arms.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(a.steps):
-                out = fn()
-            e1.record()
-            e1.synchronize()
-            ms[k].append(e0.elapsed_time(e1) / a.steps)
+    ms = _windows(arms, a.steps, a.repeats)
     loss = float(step.step(img, eps)["loss"])
     launches = {k: _launches(fn) for k, fn in arms.items()}
     med = {k: statistics.median(v) for k, v in ms.items()}
@@ -95,12 +235,7 @@ def main():
                forward_ms=dict(median=med["forward"], min=min(ms["forward"]), max=max(ms["forward"])),
                step_to_forward=med["step"] / med["forward"], launches=launches, step_tflops=tflops,
                step_mfma_frac=tflops / PEAK_BF16_TFLOPS, loss_after=loss, global_step=step.global_step)
-    line = json.dumps(rec)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            f.write(line + "\n")
+    _emit(rec, a.out)
 
 
 if __name__ == "__main__":
