@@ -8,4 +8,6 @@ from ..autoencoder import BaseAutoencoder
 
 class BaseVAE(BaseAutoencoder, metaclass=abc.ABCMeta):
     def make_discriminator(self):
-        raise NotImplementedError("GAN discriminators (VAE training) are outside the fmdiff hot path")
+        raise NotImplementedError("make_discriminator builds the MAGVIT discriminator only (VQVAE with "
+                                  "discriminator_type='magvit'); for the PatchGAN stack construct "
+                                  "fmdiff.nn.modules.vae.discriminators.PatchGANDiscriminatorND")

@@ -6,7 +6,8 @@ bf16 operand the decoder reads, so there is no channels-first round trip.  ``for
 a tape, connected to the parameters by autograd (training; ``forward`` itself carries no gradient).
 
 ``quantizer_type``: ``"classic"`` / ``"vq"`` (codebook parameter) or ``"ema"`` (codebook buffers);
-``discriminator_type`` is kept for the configs, the discriminators themselves are VAE training."""
+``make_discriminator`` builds the MAGVIT discriminator for ``discriminator_type == "magvit"``
+(``fmdiff.nn.modules.vae.discriminators``)."""
 from __future__ import annotations
 
 import os
@@ -69,6 +70,14 @@ class VQVAE(BaseVAE):
         if self.spatial_dims != 2:
             raise NotImplementedError("fmdiff VAE engine: spatial_dims=2")
         return get_vae_engine(self)
+
+    def make_discriminator(self):
+        """The reference's ``VQVAE.make_discriminator`` (``src/models/vae/vq.py``) for the MAGVIT discriminator."""
+        if self.discriminator_type == "magvit":
+            from ...nn.modules.vae.discriminators import MagvitDiscriminatorND
+            return MagvitDiscriminatorND(in_channels=self.decoder.conv_out.conv.out_channels,
+                                         spatial_dims=self.spatial_dims)
+        return super().make_discriminator()
 
     def encode(self, x: torch.Tensor, normalize: bool = False) -> torch.Tensor:
         quant_in = self._engine().encode_moments(x)

@@ -10,7 +10,8 @@ gradient goes to the first argument (logits / reconstruction / latents / predict
 ``recon_loss`` fuses ``raw_output_to_image`` with the reconstruction loss of the trainer
 (``src/pipelines/train/vae_lib.py:228-239``) and also reads the decoder head's channels-last fp32 output in place.
 
-``PerceptualLoss`` and ``PatchDiscriminator`` are not built."""
+``PerceptualLoss`` is not built; ``PatchDiscriminator`` still refuses and names
+``fmdiff.nn.modules.vae.discriminators.PatchGANDiscriminatorND``, which is."""
 from __future__ import annotations
 
 from typing import Iterable, Optional, Tuple
@@ -73,7 +74,8 @@ class PerceptualLoss(nn.Module):
 class PatchDiscriminator(nn.Module):
     def __init__(self, in_channels: int = 1, base_channels: int = 64, spatial_dims: int = 2) -> None:
         super().__init__()
-        raise NotImplementedError("GAN discriminators (VAE training) are outside the fmdiff hot path")
+        raise NotImplementedError("the PatchGAN discriminator is fmdiff.nn.modules.vae.discriminators."
+                                  "PatchGANDiscriminatorND; this name is not routed to it yet")
 
 
 def discriminator_hinge_loss(real_pred: torch.Tensor, fake_pred: torch.Tensor) -> torch.Tensor:

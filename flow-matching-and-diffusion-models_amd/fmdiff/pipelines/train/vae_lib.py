@@ -1,8 +1,9 @@
 """VAE trainer pieces (reference ``src/pipelines/train/vae_lib.py``): the scheduler factory, the discriminator
 gate and the training criterion as one object over the HIP loss kernels (``fmdiff.nn.losses.vae``,
 ``csrc/vae_loss.hip``), and one whole AutoencoderKL or VQVAE optimizer step on the engine (``VAETrainStep``).  The trainer
-loop itself is not built: the datasets, checkpoints and images around the step, the discriminator and the
-perceptual loss are missing."""
+with or without the adversarial half (a discriminator of ``fmdiff.nn.modules.vae.discriminators``).  The trainer
+loop itself is not built: the datasets, checkpoints and images around the step and the perceptual loss are missing
+(DESIGN.md section 7)."""
 from __future__ import annotations
 
 from typing import Any, Dict, Optional
@@ -126,7 +127,8 @@ class VAECriterion:
 
 class VAETrainStep:
     """One optimizer step of AutoencoderKL or VQVAE on the engine, the body of the reference's loop
-    (``vae_lib.py:198-316``) without AMP, microbatching, discriminator or perceptual terms::
+    (``vae_lib.py:198-316``) without AMP, microbatching or perceptual terms; the adversarial half runs when a
+    ``discriminator`` is given and active (see ``step``)::
 
         inputs = model.image_to_model_range(raw_images)
         rec, z, kl = model.forward_train(inputs, eps)
@@ -148,14 +150,21 @@ class VAETrainStep:
     ``kl_scale`` and Adam's bias correction only; nothing in ``step`` synchronises with the host."""
 
     def __init__(self, model, training_cfg: Dict[str, Any], model_cfg: Optional[Dict[str, Any]] = None, *,
+                 discriminator=None, disc_grad_from_generator: bool = True,
                  lr: Optional[float] = None, weight_decay: Optional[float] = None, betas=(0.9, 0.999),
                  eps: float = 1e-8) -> None:
         from ...runtime.vae_engine import get_vae_engine
         from .fused import FlatParams
         self.criterion = VAECriterion(training_cfg, model_cfg)
-        if self.criterion.gan_weight > 0:
-            raise NotImplementedError("GAN discriminators (VAE training) are outside the fmdiff hot path; set "
-                                      "gan_weight to 0")
+        if self.criterion.gan_weight > 0 and discriminator is None:
+            raise NotImplementedError("gan_weight > 0 needs a discriminator: pass discriminator= (a "
+                                      "MagvitDiscriminatorND or PatchGANDiscriminatorND of "
+                                      "fmdiff.nn.modules.vae.discriminators), or set gan_weight to 0")
+        if discriminator is not None:
+            if training_cfg.get("use_amp"):
+                raise NotImplementedError("VAETrainStep with a discriminator: use_amp (AMP / GradScaler) is not built")
+            if training_cfg.get("disc_device") is not None:
+                raise NotImplementedError("VAETrainStep: disc_device (a discriminator on another device) is not built")
         self.vq = hasattr(model, "codebook")
         if self.criterion.effective_codebook_weight != 0.0 and not self.vq:
             raise NotImplementedError("VAETrainStep: a codebook weight needs a model with a codebook (VQVAE); "
@@ -175,29 +184,118 @@ class VAETrainStep:
         self.v = torch.zeros_like(self.flat.data)
         self.global_step = 0
         self.eng.invalidate_weights()   # the parameters moved into the flat buffer
+        self.disc = discriminator
+        self.disc_grad_from_generator = bool(disc_grad_from_generator)
+        if discriminator is not None:
+            from ...runtime.disc_engine import get_disc_engine
+            out_ch = model.decoder.conv_out.conv.out_channels
+            if discriminator.in_channels != out_ch:
+                raise ValueError(f"VAETrainStep: the discriminator reads {discriminator.in_channels} channels, the "
+                                 f"decoder writes {out_ch}")
+            discriminator.train()          # as the reference's loop does at the start of every epoch
+            self.disc_eng = get_disc_engine(discriminator)
+            self.disc_flat = FlatParams(discriminator)
+            self.disc_m = torch.zeros_like(self.disc_flat.data)
+            self.disc_v = torch.zeros_like(self.disc_flat.data)
+            self.disc_step = 0             # Adam's count: active steps only (torch skips parameters without a grad)
+            dlr = training_cfg.get("disc_lr")
+            self.disc_lr = self.lr if dlr is None else float(dlr)
+            self.disc_weight_decay = 0.01  # torch.optim.AdamW's default, as the reference builds the optimizer
+            rt = str(self.criterion.recon_type).lower()
+            self.image_map = "sigmoid" if rt in ("bce", "focal", "bce_focal") else "clamp"   # raw_output_to_image
+            self.disc_eng.invalidate_weights()
 
-    def step(self, raw_images: torch.Tensor, eps: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    def step(self, raw_images: torch.Tensor, eps: Optional[torch.Tensor] = None,
+             epoch: int = 0) -> Dict[str, torch.Tensor]:
         """``raw_images``: the batch in [0, 1], NCHW fp32 on the device; ``eps``: the posterior noise (None: drawn
-        on the device; a VQVAE takes none).  Returns VAECriterion's totals as device scalars (``loss`` detached)."""
+        on the device; a VQVAE takes none); ``epoch``: the reference's epoch number, read by the discriminator gate
+        only.  Returns VAECriterion's totals as device scalars (``loss`` detached).
+
+        With a discriminator that is active at this step (``VAECriterion.disc_is_active``) the body is the
+        reference's (``vae_lib.py:248-316``): ``fake_pred = D(image(rec))`` enters the criterion, and its backward
+        reaches the VAE through the discriminator's data gradients and, as in the reference (which zeroes the
+        discriminator's gradients only at the start of the batch), also leaves ``gan_weight * d g_gan / d theta_D`` in
+        the discriminator's gradients (``disc_grad_from_generator=False``: that weight-gradient work is skipped);
+        then ``d_gan = discriminator_hinge_loss(D(raw_images), D(image(rec).detach()))`` and its backward; one AdamW
+        launch per network.  An inactive step is the step without a discriminator and leaves it untouched."""
         if self.vq and eps is not None:
             raise ValueError("VAETrainStep.step: eps is the AutoencoderKL posterior noise; a VQVAE has none")
+        active = self.disc is not None and self.criterion.disc_is_active(self.disc, epoch, self.global_step)
         self.flat.grad.zero_()
+        if active:
+            self.disc_flat.grad.zero_()
         inputs = self.model.image_to_model_range(raw_images)
         if self.vq:
             rec, aux = self.model.forward_train(inputs)
-            out = self.criterion(rec, raw_images, vq_loss=aux["vq_loss"], global_step=self.global_step)
+            kw = dict(vq_loss=aux["vq_loss"])
         else:
             rec, _, kl = self.model.forward_train(inputs, eps, sample_posterior=True)
-            out = self.criterion(rec, raw_images, kl=kl, global_step=self.global_step)
+            kw = dict(kl=kl)
+        if active:
+            kw["fake_pred"] = self.disc.forward_image(rec, self.image_map,
+                                                      param_grads=self.disc_grad_from_generator)
+        out = self.criterion(rec, raw_images, global_step=self.global_step, **kw)
         out["loss"].backward()
         out["loss"] = out["loss"].detach()
+        if active:
+            real_pred = self.disc(raw_images.detach())
+            fake_pred_detached = self.disc.forward_image(rec.detach(), self.image_map)
+            d_gan = self.criterion.discriminator_loss(real_pred, fake_pred_detached)
+            d_gan.backward()
+            out["d_gan"] = d_gan.detach()
         self.global_step += 1
         from ...runtime import ops
         n = self.n_trained
         ops.adamw(self.flat.data[:n], self.flat.grad[:n], self.m[:n], self.v[:n], self.lr, self.betas[0],
                   self.betas[1], self.eps, self.weight_decay, self.global_step)
         self.eng.invalidate_weights()
+        if active:
+            self.disc_step += 1
+            ops.adamw(self.disc_flat.data, self.disc_flat.grad, self.disc_m, self.disc_v, self.disc_lr,
+                      self.betas[0], self.betas[1], self.eps, self.disc_weight_decay, self.disc_step)
+            self.disc_eng.invalidate_weights()
         return out
+
+    def disc_state_dict(self) -> Dict[str, Any]:
+        """The discriminator optimizer's state in ``torch.optim.AdamW.state_dict()`` form (state keyed by the index
+        in ``discriminator.parameters()``)."""
+        if self.disc is None:
+            raise RuntimeError("VAETrainStep.disc_state_dict: no discriminator")
+        params = list(self.disc.parameters())
+        state = {}
+        if self.disc_step > 0:
+            for i, p in enumerate(params):
+                off, n = self.disc_flat.offsets[id(p)]
+                state[i] = {"step": torch.tensor(float(self.disc_step)),
+                            "exp_avg": self.disc_m[off:off + n].view_as(p).detach().cpu().clone(),
+                            "exp_avg_sq": self.disc_v[off:off + n].view_as(p).detach().cpu().clone()}
+        group = {"lr": self.disc_lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.disc_weight_decay,
+                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
+                 "fused": None, "decoupled_weight_decay": True, "params": list(range(len(params)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_disc_state_dict(self, sd: Dict[str, Any]) -> None:
+        """Inverse of ``disc_state_dict`` (also takes a torch AdamW state of the same discriminator)."""
+        if self.disc is None:
+            raise RuntimeError("VAETrainStep.load_disc_state_dict: no discriminator")
+        st = sd.get("state", {})
+        steps = 0
+        with torch.no_grad():
+            self.disc_m.zero_()
+            self.disc_v.zero_()
+            for i, p in enumerate(self.disc.parameters()):
+                e = st.get(i) if i in st else st.get(str(i))
+                if not e:
+                    continue
+                off, n = self.disc_flat.offsets[id(p)]
+                self.disc_m[off:off + n].copy_(torch.as_tensor(e["exp_avg"]).reshape(-1))
+                self.disc_v[off:off + n].copy_(torch.as_tensor(e["exp_avg_sq"]).reshape(-1))
+                steps = max(steps, int(float(torch.as_tensor(e["step"]))))
+        self.disc_step = steps
+        groups = sd.get("param_groups") or []
+        if groups:
+            self.disc_lr = float(groups[0].get("lr", self.disc_lr))
+            self.disc_weight_decay = float(groups[0].get("weight_decay", self.disc_weight_decay))
 
     def state_dict(self) -> Dict[str, Any]:
         """The optimizer state in ``torch.optim.AdamW.state_dict()`` form (state keyed by the index in
@@ -243,7 +341,8 @@ class VAETrainStep:
 
 def train(dataset, json_path, val_dataset=None, resume=None) -> None:
     raise NotImplementedError("The VAE trainer loop is not built: the datasets, checkpoints and sample images "
-                              "around the step, the discriminator and the perceptual loss are still missing "
-                              "(DESIGN.md section 7).  One AutoencoderKL or VQVAE optimizer step is VAETrainStep; the "
+                              "around the step and the perceptual loss are still missing "
+                              "(DESIGN.md section 7).  One AutoencoderKL or VQVAE optimizer step, with or without a "
+                              "discriminator, is VAETrainStep; the "
                               "criterion it calls is VAECriterion; the quantizer half is "
                               "VectorQuantizer*.quantize_train.")

@@ -2108,3 +2108,121 @@ def pointwise_bwd(dy, x, W, *, channels_last: bool = False, ldg: Optional[int] =
               int(x.shape[-1]) if sums else 0, _p(W), N, P, Z, E, _p(g), int(bool(channels_last)), int(ldg or 0),
               _p(dW), _p(db), int(bool(accumulate)), _p(ws) if sums else None, stream())
     return g, dW, db
+
+
+# ------------------------------------------------------------------ BatchNorm + LeakyReLU, image staging (csrc/batchnorm.hip)
+BN_ROWS = 64   # FMD_BN_ROWS
+IMAGE_MODES = {"identity": 0, "clamp": 1, "sigmoid": 2}
+
+
+def _rows_c(x, what: str):
+    """(M, C) of a contiguous bf16 channels-last activation."""
+    _need_cuda(x, what)
+    if x.dtype != BF16 or not x.is_contiguous() or x.dim() < 2:
+        raise RuntimeError(f"{what}: contiguous bf16 channels-last activations, got {x.dtype} {tuple(x.shape)}")
+    Cc = int(x.shape[-1])
+    return x.numel() // Cc, Cc
+
+
+def bn_fold(st: Optional[Stats], M: int, gamma, beta, running_mean, running_var, num_batches_tracked=None, *,
+            eps: float = 1e-5, momentum: float = 0.1, training: bool = True):
+    """nn.BatchNorm2d's statistics step on the device.  ``st``: the statistics slab of the normalised activation
+    (a conv epilogue's or ``channel_stats``'; unused in eval mode).  Training: batch mean / biased variance over the
+    M elements of a channel, the running statistics and ``num_batches_tracked`` (int64) updated in place; eval: the
+    running statistics.  Returns ``(a, b, mean_rstd)`` with ``a = gamma rstd``, ``b = beta - mean a``."""
+    _need_cuda(gamma, "bn_fold")
+    Cc = int(gamma.numel())
+    dev = gamma.device
+    a = torch.empty((Cc,), device=dev, dtype=F32)
+    b = torch.empty((Cc,), device=dev, dtype=F32)
+    mr = torch.empty((Cc, 2), device=dev, dtype=F32)
+    slab = st.slab if training else None
+    if slab is not None and (slab.dim() != 3 or slab.shape[1] != Cc or slab.shape[2] != 2 or not slab.is_contiguous()
+                             or slab.dtype != F32):
+        raise ValueError(f"bn_fold: slab {tuple(slab.shape)} is not [rows][{Cc}][2] fp32")
+    if num_batches_tracked is not None and num_batches_tracked.dtype != torch.int64:
+        raise ValueError("bn_fold: num_batches_tracked must be int64")
+    _lib.call("fmd_bn_fold", _p(slab), int(slab.shape[0]) if slab is not None else 0, Cc, int(M), _p(gamma), _p(beta),
+              float(eps), float(momentum), int(bool(training)), _p(running_mean), _p(running_var),
+              _p(num_batches_tracked), _p(a), _p(b), _p(mr), stream())
+    return a, b, mr
+
+
+def _rows_c32(x, what: str):
+    """(M, C) of a contiguous fp32 channels-last tensor (a conv's ``out_f32`` output)."""
+    _f32c(x, what, "x")
+    Cc = int(x.shape[-1])
+    return x.numel() // Cc, Cc
+
+
+def bn_stats_f32(x) -> Stats:
+    """(sum x, sum x^2) per channel and BN_ROWS-row block of an fp32 channels-last tensor: the slab ``bn_fold``
+    reads when the conv wrote fp32 (which emits no statistics of its own)."""
+    M, Cc = _rows_c32(x, "bn_stats_f32")
+    slab = torch.empty((-(-M // BN_ROWS), Cc, 2), device=x.device, dtype=F32)
+    _lib.call("fmd_bn_stats_f32", _p(x), M, Cc, _p(slab), stream())
+    return Stats(slab, BN_ROWS)
+
+
+def bn_act_fwd(x, a=None, b=None, slope: float = 0.2, out=None, split: bool = False):
+    """``lrelu(a[c] x + b[c], slope)`` as bf16 (one fma, one rounding); ``a`` None: the plain activation.
+    ``split``: ``x`` is fp32 and the result is written as two bf16 terms, ``[..., 2 C]`` with the hi terms in channels
+    [0, C) and the lo terms bf16(v - hi) in [C, 2 C) (about 16 significant bits; the walker's activation form)."""
+    if split:
+        M, Cc = _rows_c32(x, "bn_act_fwd")
+        y = torch.empty((*x.shape[:-1], 2 * Cc), device=x.device, dtype=BF16) if out is None else out
+        _lib.call("fmd_bn_act_fwd_split", _p(x), M, Cc, _p(a), _p(b), float(slope), _p(y), stream())
+        return y
+    M, Cc = _rows_c(x, "bn_act_fwd")
+    y = torch.empty_like(x) if out is None else out
+    _lib.call("fmd_bn_act_fwd", _p(x), M, Cc, _p(a), _p(b), float(slope), _p(y), stream())
+    return y
+
+
+def bn_act_bwd(dy, x, a=None, b=None, mean_rstd=None, *, slope: float = 0.2, training: bool = True, dgamma=None,
+               dbeta=None, accumulate: bool = True, skip_param_grads: bool = False, out=None, ws=None):
+    """Backward of ``bn_act_fwd`` behind a BatchNorm: returns ``dx`` (bf16, the operand of the conv's data and weight
+    gradients); ``dgamma`` / ``dbeta`` are written, or with ``accumulate`` added to, unless ``skip_param_grads``.
+    ``x``: the normalised activation, bf16 or (the walker's) fp32; ``dy`` and ``dx`` are bf16 either way."""
+    f32 = x.dtype == F32
+    M, Cc = _rows_c32(x, "bn_act_bwd") if f32 else _rows_c(x, "bn_act_bwd")
+    if _rows_c(dy, "bn_act_bwd") != (M, Cc):
+        raise ValueError(f"bn_act_bwd: dy {tuple(dy.shape)} and x {tuple(x.shape)} differ")
+    dx = torch.empty_like(dy) if out is None else out
+    if a is not None and (training or not skip_param_grads):
+        need = int(_lib.lib().fmd_bn_act_bwd_workspace(M, Cc))
+        if need < 0:
+            raise ValueError(f"bn_act_bwd: C = {Cc} must be a positive multiple of 8, M = {M}")
+        ws = _ws(ws, need, x.device, "bn_act_bwd")
+    else:
+        ws = None
+    _lib.call("fmd_bn_act_bwd_f32" if f32 else "fmd_bn_act_bwd", _p(dy), _p(x), M, Cc, _p(a), _p(b), _p(mean_rstd),
+              float(slope), int(bool(training)), _p(dx), _p(dgamma), _p(dbeta), int(bool(accumulate)),
+              int(bool(skip_param_grads)), _p(ws), stream())
+    return dx
+
+
+def image_stage(x, mode="identity", Cp: Optional[int] = None, out=None, split: bool = False):
+    """fp32 NCHW image batch -> bf16 NHWC with the channels padded to ``Cp`` (a multiple of 8; padding zero) and the
+    reference's ``raw_output_to_image`` fused: "identity", "clamp" ``(clamp(x, -1, 1) + 1) / 2``, "sigmoid".
+    ``split``: two bf16 terms per value, ``[..., 2 Cp]`` (hi | lo, as ``bn_act_fwd``)."""
+    _need_cuda(x, "image_stage")
+    _f32c(x, "image_stage", "x")
+    N, Cc = int(x.shape[0]), int(x.shape[1])
+    sp = tuple(int(v) for v in x.shape[2:])
+    Cp = int(Cp or max(8, -(-Cc // 8) * 8))
+    y = torch.empty((N, *sp, 2 * Cp if split else Cp), device=x.device, dtype=BF16) if out is None else out
+    _lib.call("fmd_image_stage_split" if split else "fmd_image_stage", _p(x), N, Cc, x[0, 0].numel(), Cp,
+              IMAGE_MODES[mode], _p(y), stream())
+    return y
+
+
+def image_stage_bwd(g, x, mode="identity"):
+    """Gradient of ``image_stage`` to the raw fp32 NCHW ``x`` from the bf16 NHWC gradient ``g`` of its output."""
+    _need_cuda(x, "image_stage_bwd")
+    _f32c(x, "image_stage_bwd", "x")
+    _, Cp = _rows_c(g, "image_stage_bwd")
+    dx = torch.empty_like(x)
+    _lib.call("fmd_image_stage_bwd", _p(g), _p(x), int(x.shape[0]), int(x.shape[1]), x[0, 0].numel(), Cp,
+              IMAGE_MODES[mode], _p(dx), stream())
+    return dx

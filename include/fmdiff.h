@@ -808,6 +808,59 @@ int fmd_pointwise_bwd(const void* dy, int32_t ldy, const void* x, int32_t ldx, c
                       int32_t Z, int32_t E, float* g, int32_t g_channels_last, int32_t ldg, float* dW, float* db,
                       int32_t accumulate, void* ws, fmd_stream_t s);
 
+/* ---- BatchNorm2d + LeakyReLU of the GAN discriminators (csrc/batchnorm.hip; reference
+ * src/nn/modules/vae/discriminators.py, src/nn/losses/vae.py PatchDiscriminator).  Activations bf16 channels-last
+ * [M][C], M = N*H*W, C % 8 == 0, 16-byte aligned; parameters and statistics fp32.  Deterministic: fp32 per lane over a
+ * fixed row range, lanes and blocks combined in a fixed order, the per-channel fold in fp64, no atomics.  Bad shapes
+ * or null operands: -1, misaligned pointers: -2, too many workgroups: -3; nothing is launched then.
+ *
+ * fmd_bn_fold: slab [rows_total][C][2] of (sum x, sum x^2) over all M elements of a channel (a conv epilogue's or
+ *   fmd_channel_stats').  training != 0: mean, biased variance; a = gamma rstd, b = beta - mean a, mean_rstd [C][2];
+ *   running_mean / running_var (unbiased, M / (M - 1)) updated with ``momentum`` and *num_batches_tracked (int64, may
+ *   be NULL) incremented on the device, as nn.BatchNorm2d does; M == 1 is an error.  training == 0: a, b and
+ *   mean_rstd from the running statistics, nothing updated, slab unused. */
+int fmd_bn_fold(const float* slab, int64_t rows_total, int32_t C, int64_t M, const float* gamma, const float* beta,
+                float eps, float momentum, int32_t training, float* running_mean, float* running_var,
+                int64_t* num_batches_tracked, float* a, float* b, float* mean_rstd, fmd_stream_t s);
+/* y = lrelu(fmaf(a[c], x, b[c]), slope), rounded once to bf16; a == b == NULL: y = lrelu(x) (a layer without norm). */
+int fmd_bn_act_fwd(const void* x, int64_t M, int32_t C, const float* a, const float* b, float slope, void* y,
+                   fmd_stream_t s);
+/* g = dy * lrelu'(fmaf(a, x, b)) (the derivative at 0 is ``slope``, as torch); S1 = sum g, S2 = sum g xhat per
+ * channel with xhat = (x - mean) rstd from mean_rstd.  training: dx = a (g - S1/M - xhat S2/M); else dx = a g;
+ * a == NULL: dx = g.  dx bf16.  dgamma (+)= S2, dbeta (+)= S1 (``accumulate`` as fmd_wgrad) unless
+ * skip_param_grads.  Launches: partial sums per FMD_BN_ROWS rows, their fp64 fold, the apply pass; ws of
+ * fmd_bn_act_bwd_workspace(M, C) bytes (needed whenever sums are: a != NULL and (training or parameter gradients)). */
+#define FMD_BN_ROWS 64
+int64_t fmd_bn_act_bwd_workspace(int64_t M, int32_t C);
+int fmd_bn_act_bwd(const void* dy, const void* x, int64_t M, int32_t C, const float* a, const float* b,
+                   const float* mean_rstd, float slope, int32_t training, void* dx, float* dgamma, float* dbeta,
+                   int32_t accumulate, int32_t skip_param_grads, void* ws, fmd_stream_t s);
+/* The discriminator's input: fp32 NCHW [N][C][HW] -> bf16 NHWC [N*HW][Cp] (Cp % 8 == 0, channels >= C zero) with
+ * raw_output_to_image fused: mode 0 identity, 1 (clamp(x, -1, 1) + 1) / 2, 2 sigmoid(x).  The backward reads the
+ * first conv's bf16 data gradient g [N*HW][Cp] and the raw x and writes fp32 NCHW: g, g 0.5 [-1 <= x <= 1], or
+ * g s (1 - s). */
+int fmd_image_stage(const float* x, int32_t N, int32_t C, int64_t HW, int32_t Cp, int32_t mode, void* out,
+                    fmd_stream_t s);
+int fmd_image_stage_bwd(const void* g, const float* x, int32_t N, int32_t C, int64_t HW, int32_t Cp, int32_t mode,
+                        float* dx, fmd_stream_t s);
+/* The two-term forms the discriminator walker runs on.  A bf16 operand moves a pre-activation by 2^-9 of its size,
+ * which flips LeakyReLU branches next to the kink and with them the gradient ("Discriminators");
+ * so an activation is carried as hi = bf16(v), lo = bf16(v - hi) in one bf16 tensor [M][2 C] (channels [0, C) hi,
+ * [C, 2 C) lo: about 16 significant bits), the conv reads both terms (and both terms of its weights) and writes fp32.
+ *   fmd_image_stage_split: fmd_image_stage with out [N*HW][2 Cp].
+ *   fmd_bn_stats_f32: slab [ceil(M / FMD_BN_ROWS)][C][2] of (sum x, sum x^2) of an fp32 [M][C] tensor, the operand
+ *     of fmd_bn_fold (an fp32 conv output carries no statistics of its own).
+ *   fmd_bn_act_fwd_split: fmd_bn_act_fwd with x fp32 [M][C] and y bf16 [M][2 C].
+ *   fmd_bn_act_bwd_f32: fmd_bn_act_bwd with x fp32 [M][C] (dy and dx stay bf16 [M][C]); same workspace. */
+int fmd_image_stage_split(const float* x, int32_t N, int32_t C, int64_t HW, int32_t Cp, int32_t mode, void* out,
+                          fmd_stream_t s);
+int fmd_bn_stats_f32(const float* x, int64_t M, int32_t C, float* slab, fmd_stream_t s);
+int fmd_bn_act_fwd_split(const float* x, int64_t M, int32_t C, const float* a, const float* b, float slope, void* y,
+                         fmd_stream_t s);
+int fmd_bn_act_bwd_f32(const void* dy, const float* x, int64_t M, int32_t C, const float* a, const float* b,
+                       const float* mean_rstd, float slope, int32_t training, void* dx, float* dgamma, float* dbeta,
+                       int32_t accumulate, int32_t skip_param_grads, void* ws, fmd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

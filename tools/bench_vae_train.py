@@ -7,7 +7,7 @@ the yardstick; the same for the VQVAE of ``configs/LDCT/LDCT_vqvae.json`` (EMA c
 M = 4 x 32 x 32 rows, D = 256 (``--arm join``; eager calls at this size measure the host's launch rate, ``--graph``
 replays a captured graph of 50 calls of each arm and measures the device).
 
-    python tools/bench_vae_train.py [--arm kl|vq_ema|vq_classic|join|all] [--out profiles/vae_train_bench.jsonl]
+    python tools/bench_vae_train.py [--arm kl|vq_ema|vq_classic|join|gan|all] [--out profiles/vae_train_bench.jsonl]
                                     [--batch 4] [--steps 10] [--repeats 5]
 
 Protocol: 3 warm-up calls of each arm, then ``--repeats`` windows per arm, alternating, each ``--steps`` calls
@@ -130,6 +130,37 @@ def bench_vq(a, qt):
                vq_after=float(out["vq"]), global_step=step.global_step), a.out)
 
 
+def bench_gan(a):
+    """``VAETrainStep.step`` of the LDCT_magvit_vqvae model block (the LDCT VQVAE with the EMA codebook) with a
+    ``MagvitDiscriminatorND(1)`` and gan_weight 0.5 active, beside the same step without the discriminator."""
+    import torch
+    from fmdiff.models.vae import VQVAE
+    from fmdiff.pipelines.train.vae_lib import VAETrainStep
+    g = torch.Generator(device="cuda").manual_seed(3)
+    img = torch.rand(a.batch, 1, 256, 256, device="cuda", generator=g)
+    steps = {}
+    for key, gw in (("gan_step", 0.5), ("plain_step", 0.0)):
+        torch.manual_seed(0)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            vae = VQVAE(quantizer_type="ema", discriminator_type="magvit", **LDCT_VQ).cuda().train()
+        disc = vae.make_discriminator().cuda() if gw else None
+        steps[key] = VAETrainStep(vae, dict(LDCT_VQ_TRAINING, gan_weight=gw), {"latent_type": "vq"},
+                                  discriminator=disc)
+    arms = {k: (lambda st=st: st.step(img)) for k, st in steps.items()}
+    ms = _windows(arms, a.steps, a.repeats)
+    out = steps["gan_step"].step(img)
+    launches = {k: _launches(fn) for k, fn in arms.items()}
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    _emit(dict(workload=f"VQVAE (LDCT_magvit_vqvae, ema codebook) + MagvitDiscriminatorND(1) adversarial train step, "
+                        f"gan_weight 0.5, 256x256, batch {a.batch}, eager",
+               disc_params=sum(p.numel() for p in steps["gan_step"].disc.parameters()),
+               steps_per_window=a.steps, windows=a.repeats, gan_step_ms=_stat(ms["gan_step"]),
+               plain_step_ms=_stat(ms["plain_step"]), gan_to_plain=med["gan_step"] / med["plain_step"],
+               launches=launches, loss_after=float(out["loss"]), g_gan_after=float(out["g_gan"]),
+               d_gan_after=float(out["d_gan"]), disc_step=steps["gan_step"].disc_step), a.out)
+
+
 def bench_join(a):
     """``ops.vq_join_bwd`` (fp32 g, the engine's arm, and bf16 g) against the four passes it replaces on the bf16
     data gradient: upcast to fp32, ``ops.vq_backward``, cast to bf16 (the 1x1 data gradient's own bf16 store is
@@ -193,7 +224,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--graph", action="store_true",
                     help="join arm: time replays of a captured graph of 50 calls (device time) instead of eager calls")
-    ap.add_argument("--arm", default="kl", choices=("kl", "vq_ema", "vq_classic", "join", "all"))
+    ap.add_argument("--arm", default="kl", choices=("kl", "vq_ema", "vq_classic", "join", "gan", "all"))
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "bench_vae_train needs a ROCm GPU"
@@ -204,6 +235,8 @@ def main():
         bench_vq(a, "ema")
     if a.arm in ("vq_classic", "all"):
         bench_vq(a, "classic")
+    if a.arm in ("gan", "all"):
+        bench_gan(a)
     if a.arm in ("join", "all"):
         bench_join(a)
 
