@@ -241,10 +241,15 @@ SIGNATURES = {
     "fmd_bn_stats_f32": [p, i64, i32, p, p],
     "fmd_bn_act_fwd_split": [p, i64, i32, p, p, f32, p, p],
     "fmd_bn_act_bwd_f32": [p, p, i64, i32, p, p, p, f32, i32, p, p, p, i32, i32, p, p],
+    "fmd_perc_stage": [p, p, i32, i32, i32, i32, i32, i32, i32, p, p],
+    "fmd_perc_stage_bwd": [p, p, i32, i32, i32, i32, i32, i32, i32, i32, p, p],
+    "fmd_perc_tap_workspace": [i32, i32, i32, i32],
+    "fmd_perc_tap_fwd": [p, i32, i32, i32, i32, i32, i32, p, p, p, f32, i32, p, p, p],
+    "fmd_perc_tap_bwd": [p, p, i32, i32, i32, i32, i32, i32, p, p, f32, p, p],
 }
 _RESTYPE = {"fmd_linear_attention_workspace": i64, "fmd_linear_attention_state": i64, "fmd_wgrad_workspace": i64, "fmd_head_wgrad_workspace": i64, "fmd_halo_tiled_size": i64, "fmd_s2d_tiled_size": i64, "fmd_s2d_tiled_size_nd": i64, "fmd_grouped_linear_bwd_workspace": i64,
              "fmd_vq_workspace": i64, "fmd_image_metrics_workspace": i64, "fmd_vae_loss_workspace": i64, "fmd_gauss_workspace": i64,
-             "fmd_pointwise_bwd_workspace": i64, "fmd_bn_act_bwd_workspace": i64}
+             "fmd_pointwise_bwd_workspace": i64, "fmd_bn_act_bwd_workspace": i64, "fmd_perc_tap_workspace": i64}
 
 _lib = None
 

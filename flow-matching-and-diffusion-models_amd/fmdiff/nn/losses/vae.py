@@ -10,8 +10,9 @@ gradient goes to the first argument (logits / reconstruction / latents / predict
 ``recon_loss`` fuses ``raw_output_to_image`` with the reconstruction loss of the trainer
 (``src/pipelines/train/vae_lib.py:228-239``) and also reads the decoder head's channels-last fp32 output in place.
 
-``PerceptualLoss`` is not built; ``PatchDiscriminator`` still refuses and names
-``fmdiff.nn.modules.vae.discriminators.PatchGANDiscriminatorND``, which is."""
+``PerceptualLoss`` refuses and names ``fmdiff.nn.losses.VGGPerceptualLoss`` (``perceptual.py``), which is built;
+``PatchDiscriminator`` refuses and names ``fmdiff.nn.modules.vae.discriminators.PatchGANDiscriminatorND``, which is
+(DESIGN.md section 7)."""
 from __future__ import annotations
 
 from typing import Iterable, Optional, Tuple
@@ -68,7 +69,8 @@ class PerceptualLoss(nn.Module):
     def __init__(self, resize: bool = False, layers: Tuple[int, ...] = (3, 8, 15, 22),
                  layer_weights: Iterable[float] = (1.0, 1.0, 1.0, 1.0)) -> None:
         super().__init__()
-        raise NotImplementedError("The VGG perceptual loss (VAE training) is outside the fmdiff hot path")
+        raise NotImplementedError("the VGG perceptual loss is fmdiff.nn.losses.VGGPerceptualLoss (the topology with "
+                                  "user-supplied weights: no torchvision, no download); this name is not routed to it")
 
 
 class PatchDiscriminator(nn.Module):

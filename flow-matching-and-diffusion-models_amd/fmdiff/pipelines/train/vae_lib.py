@@ -1,9 +1,9 @@
 """VAE trainer pieces (reference ``src/pipelines/train/vae_lib.py``): the scheduler factory, the discriminator
 gate and the training criterion as one object over the HIP loss kernels (``fmdiff.nn.losses.vae``,
-``csrc/vae_loss.hip``), and one whole AutoencoderKL or VQVAE optimizer step on the engine (``VAETrainStep``).  The trainer
-with or without the adversarial half (a discriminator of ``fmdiff.nn.modules.vae.discriminators``).  The trainer
-loop itself is not built: the datasets, checkpoints and images around the step and the perceptual loss are missing
-(DESIGN.md section 7)."""
+``csrc/vae_loss.hip``), and one whole AutoencoderKL or VQVAE optimizer step on the engine (``VAETrainStep``),
+with or without the adversarial half (a discriminator of ``fmdiff.nn.modules.vae.discriminators``) and the perceptual
+term (``fmdiff.nn.losses.VGGPerceptualLoss``).  The trainer loop itself is not built: the datasets, checkpoints and
+images around the step are missing."""
 from __future__ import annotations
 
 from typing import Any, Dict, Optional
@@ -48,16 +48,21 @@ class VAECriterion:
     """The loss composition of the reference trainer (``vae_lib.py:226-275``) from the same config keys and
     defaults::
 
-        total = recon + kl_scale(step) * kl.mean() + effective_codebook_weight * vq_loss + gan_weight * g_gan
+        total = recon + kl_scale(step) * kl.mean() + effective_codebook_weight * vq_loss
+                + perceptual_weight * perceptual + gan_weight * g_gan
 
     ``recon`` is ``recon_loss(rec, target, recon_type)``; ``kl`` the per-sample KL of ``reparameterize_kl`` /
-    ``VAEEngine.kl_forward``; ``vq_loss`` the quantizer's; ``g_gan = generator_hinge_loss(fake_pred)``.  A call
+    ``VAEEngine.kl_forward``; ``vq_loss`` the quantizer's; ``perceptual`` the ``VGGPerceptualLoss`` of the reconstructed image against the target
+    (``perceptual_weight > 0`` needs the ``perceptual=`` module at construction and refuses without it);
+    ``g_gan = generator_hinge_loss(fake_pred)``.  A call
     returns the parts as a dict of device scalars under the reference's ``totals`` keys (absent parts are a device
     zero); ``out["loss"]`` carries the gradient.  Nothing in it synchronises with the host: ``global_step`` is a
     host integer that only selects the host-side ``kl_scale`` factor."""
 
-    def __init__(self, training_cfg: Dict[str, Any], model_cfg: Optional[Dict[str, Any]] = None) -> None:
+    def __init__(self, training_cfg: Dict[str, Any], model_cfg: Optional[Dict[str, Any]] = None, *,
+                 perceptual=None) -> None:
         model_cfg = model_cfg or {}
+        self.perceptual = perceptual
         self.reg_type = str(training_cfg.get("reg_type", "kl")).lower()
         self.recon_type = training_cfg.get("recon_type", "l1")
         self.perceptual_weight = float(training_cfg.get("perceptual_weight", 0.0))
@@ -71,8 +76,9 @@ class VAECriterion:
         self.latent_type = str(model_cfg.get("latent_type", "kl")).lower()
         codebook_active = self.latent_type == "vq" or self.reg_type == "vq"
         self.effective_codebook_weight = self.codebook_weight if codebook_active else 0.0
-        if self.perceptual_weight > 0:
-            raise NotImplementedError("The VGG perceptual loss (VAE training) is outside the fmdiff hot path; set "
+        if self.perceptual_weight > 0 and perceptual is None:
+            raise NotImplementedError("perceptual_weight > 0 needs the perceptual module: pass perceptual= (a "
+                                      "fmdiff.nn.losses.VGGPerceptualLoss with its weights loaded), or set "
                                       "perceptual_weight to 0")
         if str(self.recon_type) not in ("l1", "mse", "bce", "focal", "bce_focal"):
             raise ValueError(f"Unsupported recon_type '{self.recon_type}'.")
@@ -97,11 +103,12 @@ class VAECriterion:
 
     def __call__(self, rec: torch.Tensor, target: torch.Tensor, *, kl: Optional[torch.Tensor] = None,
                  vq_loss: Optional[torch.Tensor] = None, fake_pred: Optional[torch.Tensor] = None,
-                 global_step: int = 0, channels: Optional[int] = None,
+                 perceptual: Optional[torch.Tensor] = None, global_step: int = 0, channels: Optional[int] = None,
                  grad_bf16: Optional[list] = None) -> Dict[str, torch.Tensor]:
         """``rec``: the raw decoder output (channels-first, or with ``channels=C`` the head's channels-last
         output read in place); ``target``: the image in [0, 1], channels-first.  ``fake_pred``: the
-        discriminator's logits on the reconstruction when it is active."""
+        discriminator's logits on the reconstruction when it is active.  ``perceptual``: the perceptual term of
+        this batch (a device scalar, ``VGGPerceptualLoss.forward_image(rec, image_map, target)``)."""
         zero = self._z(rec.device)
         recon = recon_loss(rec, target, self.recon_type, channels=channels, grad_bf16=grad_bf16)
         total = recon
@@ -113,11 +120,17 @@ class VAECriterion:
         if vq_loss is not None:
             vq = vq_loss
             total = total + self.effective_codebook_weight * vq
+        perc = zero
+        if perceptual is not None:
+            if self.perceptual is None:
+                raise ValueError("VAECriterion: a perceptual term needs perceptual= at construction")
+            perc = perceptual
+            total = total + self.perceptual_weight * perc
         g_gan = zero
         if fake_pred is not None:
             g_gan = generator_hinge_loss(fake_pred)
             total = total + self.gan_weight * g_gan
-        return {"loss": total, "recon": recon.detach(), "kl": kl_term.detach(), "perceptual": zero,
+        return {"loss": total, "recon": recon.detach(), "kl": kl_term.detach(), "perceptual": perc.detach(),
                 "g_gan": g_gan.detach(), "d_gan": zero, "vq": vq.detach()}
 
     def discriminator_loss(self, real_pred: torch.Tensor, fake_pred: torch.Tensor) -> torch.Tensor:
@@ -127,8 +140,9 @@ class VAECriterion:
 
 class VAETrainStep:
     """One optimizer step of AutoencoderKL or VQVAE on the engine, the body of the reference's loop
-    (``vae_lib.py:198-316``) without AMP, microbatching or perceptual terms; the adversarial half runs when a
-    ``discriminator`` is given and active (see ``step``)::
+    (``vae_lib.py:198-316``) without AMP or microbatching; the adversarial half runs when a ``discriminator`` is
+    given and active, the perceptual term when ``perceptual`` is given and ``perceptual_weight > 0`` (see
+    ``step``)::
 
         inputs = model.image_to_model_range(raw_images)
         rec, z, kl = model.forward_train(inputs, eps)
@@ -150,12 +164,19 @@ class VAETrainStep:
     ``kl_scale`` and Adam's bias correction only; nothing in ``step`` synchronises with the host."""
 
     def __init__(self, model, training_cfg: Dict[str, Any], model_cfg: Optional[Dict[str, Any]] = None, *,
-                 discriminator=None, disc_grad_from_generator: bool = True,
+                 discriminator=None, disc_grad_from_generator: bool = True, perceptual=None,
                  lr: Optional[float] = None, weight_decay: Optional[float] = None, betas=(0.9, 0.999),
                  eps: float = 1e-8) -> None:
         from ...runtime.vae_engine import get_vae_engine
         from .fused import FlatParams
-        self.criterion = VAECriterion(training_cfg, model_cfg)
+        self.criterion = VAECriterion(training_cfg, model_cfg, perceptual=perceptual)
+        if perceptual is not None:
+            if training_cfg.get("use_amp"):
+                raise NotImplementedError("VAETrainStep with a perceptual module: use_amp (AMP / GradScaler) is not "
+                                          "built")
+            if training_cfg.get("perceptual_device") is not None:
+                raise NotImplementedError("VAETrainStep: perceptual_device (a perceptual module on another device) "
+                                          "is not built")
         if self.criterion.gan_weight > 0 and discriminator is None:
             raise NotImplementedError("gan_weight > 0 needs a discriminator: pass discriminator= (a "
                                       "MagvitDiscriminatorND or PatchGANDiscriminatorND of "
@@ -201,9 +222,15 @@ class VAETrainStep:
             dlr = training_cfg.get("disc_lr")
             self.disc_lr = self.lr if dlr is None else float(dlr)
             self.disc_weight_decay = 0.01  # torch.optim.AdamW's default, as the reference builds the optimizer
-            rt = str(self.criterion.recon_type).lower()
-            self.image_map = "sigmoid" if rt in ("bce", "focal", "bce_focal") else "clamp"   # raw_output_to_image
             self.disc_eng.invalidate_weights()
+        rt = str(self.criterion.recon_type).lower()
+        self.image_map = "sigmoid" if rt in ("bce", "focal", "bce_focal") else "clamp"   # raw_output_to_image
+        self.perc = perceptual if self.criterion.perceptual_weight > 0 else None   # weight 0: never called
+        if self.perc is not None:
+            out_ch = model.decoder.conv_out.conv.out_channels
+            if out_ch not in (1, 3):
+                raise ValueError(f"VAETrainStep: the perceptual loss reads 1 or 3 channels, the decoder writes {out_ch}")
+            self.perc.eval()
 
     def step(self, raw_images: torch.Tensor, eps: Optional[torch.Tensor] = None,
              epoch: int = 0) -> Dict[str, torch.Tensor]:
@@ -217,7 +244,11 @@ class VAETrainStep:
         discriminator's gradients only at the start of the batch), also leaves ``gan_weight * d g_gan / d theta_D`` in
         the discriminator's gradients (``disc_grad_from_generator=False``: that weight-gradient work is skipped);
         then ``d_gan = discriminator_hinge_loss(D(raw_images), D(image(rec).detach()))`` and its backward; one AdamW
-        launch per network.  An inactive step is the step without a discriminator and leaves it untouched."""
+        launch per network.  An inactive step is the step without a discriminator and leaves it untouched.
+
+        With a perceptual module and ``perceptual_weight > 0`` the criterion also receives
+        ``perceptual.forward_image(rec, image_map, raw_images)`` (``vae_lib.py:241-246``), whose backward adds the
+        data gradient of the frozen stack to that of the other terms; the module itself is never changed."""
         if self.vq and eps is not None:
             raise ValueError("VAETrainStep.step: eps is the AutoencoderKL posterior noise; a VQVAE has none")
         active = self.disc is not None and self.criterion.disc_is_active(self.disc, epoch, self.global_step)
@@ -234,6 +265,8 @@ class VAETrainStep:
         if active:
             kw["fake_pred"] = self.disc.forward_image(rec, self.image_map,
                                                       param_grads=self.disc_grad_from_generator)
+        if self.perc is not None:
+            kw["perceptual"] = self.perc.forward_image(rec, self.image_map, raw_images)
         out = self.criterion(rec, raw_images, global_step=self.global_step, **kw)
         out["loss"].backward()
         out["loss"] = out["loss"].detach()
@@ -341,8 +374,8 @@ class VAETrainStep:
 
 def train(dataset, json_path, val_dataset=None, resume=None) -> None:
     raise NotImplementedError("The VAE trainer loop is not built: the datasets, checkpoints and sample images "
-                              "around the step and the perceptual loss are still missing "
+                              "around the step are still missing "
                               "(DESIGN.md section 7).  One AutoencoderKL or VQVAE optimizer step, with or without a "
-                              "discriminator, is VAETrainStep; the "
+                              "discriminator and the perceptual term, is VAETrainStep; the "
                               "criterion it calls is VAECriterion; the quantizer half is "
                               "VectorQuantizer*.quantize_train.")

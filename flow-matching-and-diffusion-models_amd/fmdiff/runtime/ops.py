@@ -2226,3 +2226,112 @@ def image_stage_bwd(g, x, mode="identity"):
     _lib.call("fmd_image_stage_bwd", _p(g), _p(x), int(x.shape[0]), int(x.shape[1]), x[0, 0].numel(), Cp,
               IMAGE_MODES[mode], _p(dx), stream())
     return dx
+
+
+# ------------------------------------------------------------------ VGG perceptual loss (csrc/perceptual.hip)
+def _perc_hw(size, what: str):
+    if size is None:
+        return None
+    hw = (int(size), int(size)) if isinstance(size, int) else tuple(int(v) for v in size)
+    if len(hw) != 2 or hw[0] < 1 or hw[1] < 1:
+        raise ValueError(f"{what}: size must be a positive int or (h, w), got {size!r}")
+    return hw
+
+
+def _perc_images(recon, target, what: str):
+    _f32c(recon, what, "recon")
+    if target is not None:
+        _f32c(target, what, "target")
+        if target.shape != recon.shape:
+            raise ValueError(f"{what}: recon {tuple(recon.shape)} and target {tuple(target.shape)} differ")
+    if recon.dim() != 4 or recon.shape[1] not in (1, 3) or recon.numel() == 0:
+        raise ValueError(f"{what}: images [N, 1 or 3, H, W], got {tuple(recon.shape)}")
+    return tuple(int(v) for v in recon.shape)
+
+
+def perc_stage(recon, target, mode="identity", size=None):
+    """The perceptual loss's input: fp32 NCHW ``recon`` and ``target`` (1 or 3 channels) -> one two-term bf16 batch
+    ``[2 N, Ho, Wo, 16]`` (recon first; 8 hi | 8 lo channels, one channel repeated to three).  ``mode``: the image map
+    (``IMAGE_MODES``) of the recon half, the target is used as given; ``size``: bilinear resize to ``(Ho, Wo)`` with
+    torch's ``align_corners=False`` rule."""
+    N, Cc, Hs, Ws = _perc_images(recon, target, "perc_stage")
+    Ho, Wo = _perc_hw(size, "perc_stage") or (Hs, Ws)
+    out = torch.empty((2 * N, Ho, Wo, 16), device=recon.device, dtype=BF16)
+    _lib.call("fmd_perc_stage", _p(recon), _p(target), N, Cc, Hs, Ws, Ho, Wo, IMAGE_MODES[mode], _p(out), stream())
+    return out
+
+
+def perc_stage_bwd(g, recon, mode="identity"):
+    """Gradient of ``perc_stage`` to the raw fp32 NCHW ``recon`` from the bf16 ``[N, Ho, Wo, Cp]`` gradient ``g`` of
+    the recon half of its output (the first conv's data gradient)."""
+    N, Cc, Hs, Ws = _perc_images(recon, None, "perc_stage_bwd")
+    _, Cp = _rows_c(g, "perc_stage_bwd")
+    if g.dim() != 4 or g.shape[0] != N:
+        raise ValueError(f"perc_stage_bwd: g [{N}, Ho, Wo, Cp], got {tuple(g.shape)}")
+    dx = torch.empty_like(recon)
+    _lib.call("fmd_perc_stage_bwd", _p(g), _p(recon), N, Cc, Hs, Ws, int(g.shape[1]), int(g.shape[2]), Cp,
+              IMAGE_MODES[mode], _p(dx), stream())
+    return dx
+
+
+def perc_tap_fwd(y, C: int, *, pool: bool = False, want_out: bool = True, save: bool = True, weight: float = 1.0,
+                 value=None, loss=None, first: bool = True, ws=None, out=None, sgn=None):
+    """The feature tap on a conv's fp32 output ``y [2 N, H, W, Cp]`` (recon rows first): ``value`` (a device fp32
+    scalar, made if None) receives ``mean |relu(y_rec) - relu(y_tgt)|`` over the ``C`` real channels, ``loss`` (if
+    given) ``weight * value`` (``first``) or that added to it.  Returns ``(out, sgn, value)``: ``out`` the next conv's
+    two-term operand ``relu(y)`` for all 2 N images, behind a 2x2 stride-2 max pool with ``pool`` (None without
+    ``want_out``); ``sgn`` the int8 sign of the difference ``[N, H, W, Cp]`` that ``perc_tap_bwd`` reads (None without
+    ``save``)."""
+    _f32c(y, "perc_tap_fwd", "y")
+    if y.dim() != 4 or y.shape[0] % 2 or y.shape[0] < 2:
+        raise ValueError(f"perc_tap_fwd: y [2 N, H, W, Cp], got {tuple(y.shape)}")
+    N, H, W, Cp = int(y.shape[0]) // 2, int(y.shape[1]), int(y.shape[2]), int(y.shape[3])
+    need = int(_lib.lib().fmd_perc_tap_workspace(N, H, W, Cp))
+    if need < 0 or not 1 <= int(C) <= Cp:
+        raise ValueError(f"perc_tap_fwd: Cp = {Cp} must be a positive multiple of 8 and 1 <= C = {C} <= Cp")
+    if want_out and pool and (H < 2 or W < 2):
+        raise ValueError(f"perc_tap_fwd: a {H}x{W} map is too small for the 2x2 pool")
+    dev = y.device
+    ws = _ws(ws, need, dev, "perc_tap_fwd")
+    oshape = (2 * N, H // 2, W // 2, 2 * Cp) if pool else (2 * N, H, W, 2 * Cp)
+    if not want_out:
+        out = None
+    elif out is None:
+        out = torch.empty(oshape, device=dev, dtype=BF16)
+    elif tuple(out.shape) != oshape or out.dtype != BF16 or not out.is_contiguous():
+        raise ValueError(f"perc_tap_fwd: out must be bf16 {oshape}")
+    if not save:
+        sgn = None
+    elif sgn is None:
+        sgn = torch.empty((N, H, W, Cp), device=dev, dtype=torch.int8)
+    elif tuple(sgn.shape) != (N, H, W, Cp) or sgn.dtype != torch.int8 or not sgn.is_contiguous():
+        raise ValueError(f"perc_tap_fwd: sgn must be int8 {(N, H, W, Cp)}")
+    if value is None:
+        value = torch.empty((), device=dev, dtype=F32)
+    _lib.call("fmd_perc_tap_fwd", _p(y), N, H, W, Cp, int(C), int(bool(pool)), _p(out), _p(sgn), _p(ws),
+              float(weight), int(bool(first)), _p(value), _p(loss), stream())
+    return out, sgn, value
+
+
+def perc_tap_bwd(y_rec, sgn, C: int, g_loss, *, weight: float = 1.0, g_below=None, pool: bool = False, out=None):
+    """Backward of the tap, recon half: bf16 ``dy [N, H, W, Cp]`` of the tapped conv's output from the saved recon
+    rows ``y_rec`` (fp32), ``sgn``, the device scalar ``g_loss`` and the gradient ``g_below`` of the tap's output
+    (``[N, H/2, W/2, Cp]`` with ``pool``: routed to the first maximum of each window; None: the last tap)."""
+    _f32c(y_rec, "perc_tap_bwd", "y_rec")
+    _f32c(g_loss, "perc_tap_bwd", "g_loss")
+    _need_cuda(sgn, "perc_tap_bwd")
+    if y_rec.dim() != 4 or sgn.dtype != torch.int8 or sgn.shape != y_rec.shape or not sgn.is_contiguous():
+        raise ValueError(f"perc_tap_bwd: y_rec [N, H, W, Cp] fp32 and sgn int8 of that shape, got "
+                         f"{tuple(y_rec.shape)} and {sgn.dtype} {tuple(sgn.shape)}")
+    N, H, W, Cp = (int(v) for v in y_rec.shape)
+    if Cp % 8 or not 1 <= int(C) <= Cp or g_loss.numel() != 1:
+        raise ValueError(f"perc_tap_bwd: Cp = {Cp} a multiple of 8, 1 <= C = {C} <= Cp, g_loss one element")
+    if g_below is not None:
+        want = (N, H // 2, W // 2, Cp) if pool else (N, H, W, Cp)
+        _rows_c(g_below, "perc_tap_bwd")
+        if tuple(g_below.shape) != want or 0 in want:
+            raise ValueError(f"perc_tap_bwd: g_below {tuple(g_below.shape)}, expected {want}")
+    dy = torch.empty((N, H, W, Cp), device=y_rec.device, dtype=BF16) if out is None else out
+    _lib.call("fmd_perc_tap_bwd", _p(y_rec), _p(sgn), N, H, W, Cp, int(C), int(bool(pool)), _p(g_below), _p(g_loss),
+              float(weight), _p(dy), stream())
+    return dy

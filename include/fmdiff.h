@@ -861,6 +861,40 @@ int fmd_bn_act_bwd_f32(const void* dy, const float* x, int64_t M, int32_t C, con
                        const float* mean_rstd, float slope, int32_t training, void* dx, float* dgamma, float* dbeta,
                        int32_t accumulate, int32_t skip_param_grads, void* ws, fmd_stream_t s);
 
+/* ---- VGG perceptual loss of VAE training (csrc/perceptual.hip; reference src/nn/losses/vae.py:22-72): staging, the
+ * feature tap and the 2x2 max pool around a conv stack that runs on the two-term route above (the untapped ReLUs are
+ * fmd_bn_act_fwd_split / fmd_bn_act_bwd_f32 with slope 0).  Recon and target travel as ONE batch of 2 N images, recon
+ * first.  Deterministic: fixed-order sums (fp64 for the loss), no atomics.  Bad shapes or null operands: -1,
+ * misaligned pointers: -2, too many workgroups: -3; nothing is launched then.
+ *
+ * fmd_perc_stage: recon, target fp32 NCHW [N][C][Hs][Ws], C 1 or 3 -> out bf16 [2 N][Ho][Wo][16], 8 hi | 8 lo channels
+ *   (hi = bf16(v), lo = bf16(v - hi)); one channel is repeated to three, channels 3..7 are zero.  The image map
+ *   ``mode`` (fmd_image_stage) applies to the recon half only.  (Ho, Wo) != (Hs, Ws): bilinear resize, torch's
+ *   align_corners=False rule: source coordinate max((o + 1/2) in / out - 1/2, 0), upper neighbour clamped to the edge.
+ * fmd_perc_stage_bwd: g bf16 [N][Ho][Wo][Cp] (gradient of the first conv's input, recon half; channels 0..2 read) ->
+ *   dx fp32 [N][C][Hs][Ws] of the raw recon: each source pixel adds the destination pixels that read it (rows, then
+ *   columns ascending; the range comes from the inverted coordinate map), the repeated channels are added as
+ *   (g0 + g1) + g2, then the map's derivative as fmd_image_stage_bwd. */
+int fmd_perc_stage(const float* recon, const float* target, int32_t N, int32_t C, int32_t Hs, int32_t Ws, int32_t Ho,
+                   int32_t Wo, int32_t mode, void* out, fmd_stream_t s);
+int fmd_perc_stage_bwd(const void* g, const float* recon, int32_t N, int32_t C, int32_t Hs, int32_t Ws, int32_t Ho,
+                       int32_t Wo, int32_t Cp, int32_t mode, float* dx, fmd_stream_t s);
+/* fmd_perc_tap_fwd: y fp32 [2 N][H][W][Cp], a tapped conv's output with its bias.  Over the C real channels:
+ *   *value = (float)(sum |relu(y_rec) - relu(y_tgt)| / (N C H W)) (the difference one fp32 rounding, the sum fp64), and
+ *   *loss = weight *value (first != 0) or *loss + weight *value (loss may be NULL).  sgn (int8 [N][H][W][Cp], may be
+ *   NULL) receives sign(relu(y_rec) - relu(y_tgt)), 0 in padding channels.  out (may be NULL) is the next conv's
+ *   two-term operand for all 2 N images: [2 N][H][W][2 Cp] with relu(y), or with pool != 0 [2 N][H/2][W/2][2 Cp] with
+ *   relu of the 2x2 stride-2 maximum of y (odd sizes floor, as nn.MaxPool2d(2, 2)).  ws: fmd_perc_tap_workspace bytes.
+ * fmd_perc_tap_bwd: recon half only.  dy bf16 [N][H][W][Cp] =
+ *   [y_rec > 0] (g_loss[0] weight / (N C H W) sgn + below), with below = 0 (g_below NULL), g_below [N][H][W][Cp]
+ *   (pool == 0), or g_below [N][H/2][W/2][Cp] routed to the first maximum of y_rec in its window in row-major order
+ *   (pool != 0; pixels the floor leaves outside every window get none). */
+int64_t fmd_perc_tap_workspace(int32_t N, int32_t H, int32_t W, int32_t Cp);
+int fmd_perc_tap_fwd(const float* y, int32_t N, int32_t H, int32_t W, int32_t Cp, int32_t C, int32_t pool, void* out,
+                     void* sgn, void* ws, float weight, int32_t first, float* value, float* loss, fmd_stream_t s);
+int fmd_perc_tap_bwd(const float* y_rec, const void* sgn, int32_t N, int32_t H, int32_t W, int32_t Cp, int32_t C,
+                     int32_t pool, const void* g_below, const float* g_loss, float weight, void* dy, fmd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

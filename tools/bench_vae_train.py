@@ -5,9 +5,12 @@ the yardstick; the same for the VQVAE of ``configs/LDCT/LDCT_vqvae.json`` (EMA c
 ``LDCT_vqvae_original.json`` (classic codebook) with ``VAEEngine.vq_forward`` as the yardstick (``--arm vq_ema`` /
 ``vq_classic``); and an A/B of the latent-join kernel against the four-pass composition it replaces at
 M = 4 x 32 x 32 rows, D = 256 (``--arm join``; eager calls at this size measure the host's launch rate, ``--graph``
-replays a captured graph of 50 calls of each arm and measures the device).
+replays a captured graph of 50 calls of each arm and measures the device).  ``--perceptual`` (or ``--arm perc``)
+times ``VGGPerceptualLoss`` forward + backward alone (full-width VGG16 stack, random weights, batch 8,
+1 x 256 x 256 -> 224 x 224), the AutoencoderKL step with and without the term (perceptual_weight 1.0), and records the
+kernel ``fmd_conv_plan`` chooses for each of the ten convs at 224 x 224 and batch 8.
 
-    python tools/bench_vae_train.py [--arm kl|vq_ema|vq_classic|join|gan|all] [--out profiles/vae_train_bench.jsonl]
+    python tools/bench_vae_train.py [--arm kl|vq_ema|vq_classic|join|gan|perc|all] [--perceptual] [--out profiles/vae_train_bench.jsonl]
                                     [--batch 4] [--steps 10] [--repeats 5]
 
 Protocol: 3 warm-up calls of each arm, then ``--repeats`` windows per arm, alternating, each ``--steps`` calls
@@ -161,6 +164,54 @@ def bench_gan(a):
                d_gan_after=float(out["d_gan"]), disc_step=steps["gan_step"].disc_step), a.out)
 
 
+def bench_perc(a):
+    """The perceptual term: alone (forward + backward to the image), in the AutoencoderKL step, and its conv plan."""
+    import torch
+    from fmdiff.models.vae import AutoencoderKL
+    from fmdiff.nn.losses import VGGPerceptualLoss
+    from fmdiff.pipelines.train.vae_lib import VAETrainStep
+    from fmdiff.runtime.perc_engine import get_perc_engine
+    torch.manual_seed(0)
+    P = VGGPerceptualLoss(resize=True).cuda()
+    g = torch.Generator(device="cuda").manual_seed(3)
+    img8 = torch.rand(8, 1, 256, 256, device="cuda", generator=g)
+    rec8 = (img8 + 0.1 * torch.randn(img8.shape, device="cuda", generator=g)).clamp(0, 1)
+    plans = []
+    with torch.no_grad():
+        get_perc_engine(P).forward(rec8, img8, plan_out=plans)
+    names = {1: "igemm", 2: "halo8", 3: "halo9"}
+    table = [dict(conv=i, out=list(shape), kernel=names.get(pl.kernel, pl.kernel), tile_rows=pl.tile_rows, bco=pl.bco,
+                  bpx=pl.bpx, splits=sp) for i, shape, pl, sp in plans]
+
+    def alone():
+        r = rec8.clone().requires_grad_()
+        P(r, img8).backward()
+
+    def forward_only():
+        with torch.no_grad():
+            P(rec8, img8)
+
+    img = torch.rand(a.batch, 1, 256, 256, device="cuda", generator=g)
+    eps = torch.randn(a.batch, 4, 32, 32, device="cuda", generator=g)
+    steps = {}
+    for key, w in (("perc_step", 1.0), ("plain_step", 0.0)):
+        torch.manual_seed(0)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            vae = AutoencoderKL(**LDCT_VAE).cuda()
+        steps[key] = VAETrainStep(vae, dict(LDCT_TRAINING, perceptual_weight=w), perceptual=P if w else None)
+    arms = {"perc_fwd_bwd_b8": alone, "perc_fwd_b8": forward_only}
+    arms.update({k: (lambda st=st: st.step(img, eps)) for k, st in steps.items()})
+    ms = _windows(arms, a.steps, a.repeats)
+    out = steps["perc_step"].step(img, eps)
+    launches = {k: _launches(fn) for k, fn in arms.items()}
+    _emit(dict(workload=f"VGGPerceptualLoss (VGG16 widths, random weights, 1x256x256 -> 224x224): alone at batch 8; in "
+                        f"the AutoencoderKL (LDCT_autoencoder_kl) train step at batch {a.batch}, eager",
+               steps_per_window=a.steps, windows=a.repeats, ms={k: _stat(v) for k, v in ms.items()},
+               launches=launches, loss_after=float(out["loss"]), perceptual_after=float(out["perceptual"]),
+               conv_plan=table), a.out)
+
+
 def bench_join(a):
     """``ops.vq_join_bwd`` (fp32 g, the engine's arm, and bf16 g) against the four passes it replaces on the bf16
     data gradient: upcast to fp32, ``ops.vq_backward``, cast to bf16 (the 1x1 data gradient's own bf16 store is
@@ -224,7 +275,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--graph", action="store_true",
                     help="join arm: time replays of a captured graph of 50 calls (device time) instead of eager calls")
-    ap.add_argument("--arm", default="kl", choices=("kl", "vq_ema", "vq_classic", "join", "gan", "all"))
+    ap.add_argument("--arm", default="kl", choices=("kl", "vq_ema", "vq_classic", "join", "gan", "perc", "all"))
+    ap.add_argument("--perceptual", action="store_true", help="also run the perceptual-term arm (--arm perc)")
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "bench_vae_train needs a ROCm GPU"
@@ -237,6 +289,8 @@ def main():
         bench_vq(a, "classic")
     if a.arm in ("gan", "all"):
         bench_gan(a)
+    if a.arm in ("perc", "all") or a.perceptual:
+        bench_perc(a)
     if a.arm in ("join", "all"):
         bench_join(a)
 
