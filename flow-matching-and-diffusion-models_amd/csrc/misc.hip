@@ -1155,7 +1155,9 @@ int fmd_resample2(const void* src, int32_t N, int32_t Dl, int32_t Hl, int32_t Wl
                   fmd_stream_t s) {
   if (N < 1 || C < 1 || Dl < 1 || Hl < 1 || Wl < 1 || fz < 1 || fz > 2 || fy < 1 || fy > 2 || fx < 1 || fx > 2)
     return -1;
-  if (Dh < fz * Dl || Hh < fy * Hl || Wh < fx * Wl || Dh > fz * Dl + 1 || Hh > fy * Hl + 1 || Wh > fx * Wl + 1)
+  // a factor-2 dim may carry one odd high index (floor pooling); a factor-1 dim has equal extents
+  if (Dh < fz * Dl || Hh < fy * Hl || Wh < fx * Wl || Dh > fz * Dl + (fz - 1) || Hh > fy * Hl + (fy - 1) ||
+      Wh > fx * Wl + (fx - 1))
     return -1;
   const long long work = (long long)N * (up ? (long long)Dh * Hh * Wh : (long long)Dl * Hl * Wl) * C;
   LAUNCH(resample2_kernel, grid_for(work), (const bf16r*)src, N, Dl, Hl, Wl, Dh, Hh, Wh, C, fz, fy, fx, up, scale,

@@ -467,7 +467,8 @@ int fmd_nhwc_to_nchw(const void* y, int32_t src_f32, int32_t N, int32_t C, int32
  * (src/nn/ops/pooling.py:33-53, scale 1/2^d; DownsampleND(use_conv=False), upsampling.py:52-58) and the
  * nearest-x2 data gradient (scale 1).  up = 1: dst[high] (+)= scale * src[high >> 1] -- UpsampleND(use_conv=
  * False)'s F.interpolate(scale_factor=2, mode="nearest") (upsampling.py:24-29, scale 1) and the avg-pool data
- * gradient (scale 1/2^d).  High extents are 2*low or 2*low + 1 (floor pooling of an odd extent). */
+ * gradient (scale 1/2^d).  High extents are 2*low or 2*low + 1 (floor pooling of an odd extent) along a
+ * factor-2 dim and equal to the low extent along a factor-1 dim; anything else returns -1. */
 int fmd_resample2(const void* src, int32_t N, int32_t Dl, int32_t Hl, int32_t Wl, int32_t Dh, int32_t Hh, int32_t Wh,
                   int32_t C, int32_t fz, int32_t fy, int32_t fx, int32_t up, float scale, void* dst, int32_t acc,
                   fmd_stream_t s);
