@@ -61,18 +61,10 @@ def _broadcast_path(path: Optional[Path]) -> Path:
 
 def _save_grid(t: torch.Tensor, path: Path) -> None:
     """Square-ish PNG grid of [N, C, H, W] images in [0, 1] (reference evaluation_utils.make_grid/save_image)."""
-    import numpy as np
-    from PIL import Image
     n = t.shape[0]
     rows = max(1, int(math.sqrt(n)))
     cols = max(1, n // rows)
-    x = t[: rows * cols].detach().float().clamp(0, 1).cpu()
-    if x.shape[1] == 1:
-        x = x.expand(-1, 3, -1, -1)
-    c, h, w = x.shape[1:]
-    grid = x.reshape(rows, cols, c, h, w).permute(2, 0, 3, 1, 4).reshape(c, rows * h, cols * w)
-    path.parent.mkdir(parents=True, exist_ok=True)
-    Image.fromarray((grid.numpy() * 255.0).clip(0, 255).astype(np.uint8).transpose(1, 2, 0)).save(path)
+    U.save_image(U.make_grid(t.detach().float(), rows, cols), path)
 
 
 def run_training(dataset, json_path, val_dataset=None, resume: Optional[str] = None, *, objective: str,

@@ -23,7 +23,7 @@ import torch
 import torch.distributed as dist
 
 __all__ = ["load_json_config", "save_json_config", "allocate_run_dir", "set_seed", "resolve_device",
-           "resolve_batch_size", "save_checkpoint", "maybe_load_checkpoint", "setup_distributed",
+           "resolve_batch_size", "save_checkpoint", "latest_checkpoint", "maybe_load_checkpoint", "setup_distributed",
            "is_distributed", "is_main_process", "get_rank", "get_world_size"]
 
 
@@ -90,6 +90,18 @@ def save_checkpoint(state: dict, path) -> None:
     tmp = path.with_name(path.name + ".tmp")
     torch.save(state, tmp)
     os.replace(tmp, path)
+
+
+def latest_checkpoint(output_dir) -> Optional[Path]:
+    """The newer of ``vae_last.pt`` / ``vae_best.pt`` in ``output_dir``; without either, its newest ``*.pt``; None
+    if there is none."""
+    output_dir = Path(output_dir)
+    candidates = [p for p in (output_dir / "vae_last.pt", output_dir / "vae_best.pt") if p.exists()]
+    if not candidates:
+        candidates = list(output_dir.glob("*.pt"))
+    if not candidates:
+        return None
+    return max(candidates, key=lambda p: p.stat().st_mtime)
 
 
 def setup_distributed(backend: Optional[str] = None) -> bool:
