@@ -311,10 +311,37 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 // Same update with the step count read from device memory and the LR of
 // get_cosine_schedule_with_warmup (flow_matching_lib.py:76-79) computed on device,
 // so a captured train-step graph replays with the right schedule.
-__global__ void adamw_sched_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                   float* __restrict__ v, long long n, const int* __restrict__ step_ctr,
-                                   float base_lr, int warmup, int total, float b1, float b2, float eps, float wd,
-                                   float grad_scale, int vec) {
+//
+// EMA (fmd_adamw_sched_ema): the same pass also moves an exponential moving average of the parameters towards
+// the value just computed (still in its register), ema += (1 - d) * (p_new - ema), with the decay d warmed up as
+// min(decay, (1 + s) / (10 + s)) from the same device step count s.  Every EMA operation is rounded on its own (no
+// FMA contraction), so separate fp32 torch ops on the CPU reproduce the bits; p, m, v are computed by the same
+// expressions with or without it.
+__device__ __forceinline__ float ema_one_minus_decay(int s, float decay, int ema_warmup) {
+#pragma clang fp contract(off)
+  float d = decay;
+  if (ema_warmup) {
+    const float sf = (float)s;
+    const float w = (sf + 1.0f) / (sf + 10.0f);   // IEEE fp32 division (hipcc's default for / on float)
+    d = w < d ? w : d;
+  }
+  return 1.0f - d;
+}
+
+__device__ __forceinline__ float ema_lerp(float ema, float p_new, float omd) {
+#pragma clang fp contract(off)
+  const float diff = p_new - ema;
+  const float inc = omd * diff;
+  return ema + inc;
+}
+
+template <bool EMA>
+__device__ __forceinline__ void adamw_sched_body(float* __restrict__ p, const float* __restrict__ g,
+                                                 float* __restrict__ m, float* __restrict__ v, long long n,
+                                                 const int* __restrict__ step_ctr, float base_lr, int warmup,
+                                                 int total, float b1, float b2, float eps, float wd,
+                                                 float grad_scale, int vec, float* __restrict__ ema, float decay,
+                                                 int ema_warmup) {
   const int step = step_ctr[0] + 1;          // optimizer.step() count, 1-based
   const int s = step - 1;                    // lr_scheduler.step() calls so far
   double lam;
@@ -328,6 +355,7 @@ __global__ void adamw_sched_kernel(float* __restrict__ p, const float* __restric
   const float lr = (float)(base_lr * lam);
   const float bc1 = (float)(1.0 - pow((double)b1, step));
   const float bc2s = sqrtf((float)(1.0 - pow((double)b2, step)));
+  const float omd = EMA ? ema_one_minus_decay(s, decay, ema_warmup) : 0.f;
   auto upd = [&](float& pv, float gv, float& mv, float& vv) {
     gv *= grad_scale;
     pv = pv * (1.f - lr * wd);
@@ -351,6 +379,12 @@ __global__ void adamw_sched_kernel(float* __restrict__ p, const float* __restric
     ((f32x4*)p)[i] = pv;
     ((f32x4*)m)[i] = mv;
     ((f32x4*)v)[i] = vv;
+    if (EMA) {
+      f32x4 ev = ((const f32x4*)ema)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ev[e] = ema_lerp(ev[e], pv[e], omd);
+      ((f32x4*)ema)[i] = ev;
+    }
   }
   for (long long i = 4 * n4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     float pv = p[i], mv = m[i], vv = v[i];
@@ -358,7 +392,25 @@ __global__ void adamw_sched_kernel(float* __restrict__ p, const float* __restric
     p[i] = pv;
     m[i] = mv;
     v[i] = vv;
+    if (EMA) ema[i] = ema_lerp(ema[i], pv, omd);
   }
+}
+
+__global__ void adamw_sched_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                   float* __restrict__ v, long long n, const int* __restrict__ step_ctr,
+                                   float base_lr, int warmup, int total, float b1, float b2, float eps, float wd,
+                                   float grad_scale, int vec) {
+  adamw_sched_body<false>(p, g, m, v, n, step_ctr, base_lr, warmup, total, b1, b2, eps, wd, grad_scale, vec, nullptr,
+                          0.f, 0);
+}
+
+__global__ void adamw_sched_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                       float* __restrict__ v, long long n, const int* __restrict__ step_ctr,
+                                       float base_lr, int warmup, int total, float b1, float b2, float eps, float wd,
+                                       float grad_scale, int vec, float* __restrict__ ema, float decay,
+                                       int ema_warmup) {
+  adamw_sched_body<true>(p, g, m, v, n, step_ctr, base_lr, warmup, total, b1, b2, eps, wd, grad_scale, vec, ema, decay,
+                         ema_warmup);
 }
 
 // FlowMatchEuler: x += (sigma[i+1] - sigma[i]) * v   (fp32), then write the next model input
@@ -1082,6 +1134,16 @@ int fmd_adamw_sched(float* p, const float* g, float* m, float* v, int64_t n, con
                     reinterpret_cast<uintptr_t>(v)) & 15) == 0;
   LAUNCH(adamw_sched_kernel, grid_for(vec ? n / 4 : n, 256, 8192), p, g, m, v, (long long)n, step_ctr, base_lr, warmup,
          total, beta1, beta2, eps, wd, grad_scale, vec);
+}
+
+int fmd_adamw_sched_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const int32_t* step_ctr,
+                        float base_lr, int32_t warmup, int32_t total, float beta1, float beta2, float eps, float wd,
+                        float grad_scale, float ema_decay, int32_t ema_warmup, fmd_stream_t s) {
+  if (!ema || !(ema_decay >= 0.f && ema_decay < 1.f)) return -1;
+  const int vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                    reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(ema)) & 15) == 0;
+  LAUNCH(adamw_sched_ema_kernel, grid_for(vec ? n / 4 : n, 256, 8192), p, g, m, v, (long long)n, step_ctr, base_lr,
+         warmup, total, beta1, beta2, eps, wd, grad_scale, vec, ema, ema_decay, ema_warmup ? 1 : 0);
 }
 
 int fmd_flow_euler(float* x, const float* v, int32_t Kpad, const float* sigmas, const int32_t* index, int32_t N,

@@ -177,6 +177,7 @@ SIGNATURES = {
     "fmd_add_bf16": [p, p, i64, p],
     "fmd_timestep_embedding": [p, i32, i32, i32, i32, f32, f32, i32, p, p],
     "fmd_adamw_sched": [p, p, p, p, i64, p, f32, i32, i32, f32, f32, f32, f32, f32, p],
+    "fmd_adamw_sched_ema": [p, p, p, p, p, i64, p, f32, i32, i32, f32, f32, f32, f32, f32, f32, i32, p],
     "fmd_linear": [p, i32, i32, p, p, i32, i32, p, i32, p],
     "fmd_linear_bwd": [p, i32, i32, p, i32, i32, p, i32, p, i32, p, p, p],
     "fmd_silu_bwd_f32": [p, p, p, i64, p],

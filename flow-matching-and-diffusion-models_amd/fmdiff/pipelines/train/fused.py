@@ -19,6 +19,7 @@ buckets.
 """
 from __future__ import annotations
 
+import contextlib
 import functools
 import math
 import time
@@ -133,7 +134,11 @@ class FusedTrainStep:
     def __init__(self, model, *, objective: str = "flow_matching", lr: float = 1e-4, weight_decay: float = 0.0,
                  warmup: int = 500, total_steps: int = 10 ** 9, num_train_timesteps: int = 1000,
                  grad_accum: int = 1, betas=(0.9, 0.999), eps: float = 1e-8, ddpm_scheduler=None,
-                 process_group=None, allreduce_buckets: int = 4, overlap_allreduce: Optional[bool] = None):
+                 process_group=None, allreduce_buckets: int = 4, overlap_allreduce: Optional[bool] = None,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
+        """``ema_decay`` (in [0, 1); None: no EMA): keep an exponential moving average of the parameters in
+        ``self.ema``, a flat buffer laid out like ``self.flat.data``, updated by the AdamW launch itself
+        (fmd_adamw_sched_ema) with the decay warmed up as min(decay, (1 + s) / (10 + s)) when ``ema_warmup``."""
         self.model = model
         self.eng = get_engine(model)
         world = world_size(process_group)
@@ -155,6 +160,14 @@ class FusedTrainStep:
         dev = self.flat.data.device
         self.m = torch.zeros_like(self.flat.data)
         self.v = torch.zeros_like(self.flat.data)
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        # data parallel: every rank applies the same update to the same parameters, so the EMAs stay identical
+        # without any exchange
+        self.ema = self.flat.data.clone() if self.ema_decay is not None else None
+        self._swapped = False
         self.step_ctr = torch.zeros(1, dtype=torch.int32, device=dev)
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
         # sum over chunks of loss * chunk size (flow_matching_lib.py:174), kept on the device so the step never
@@ -219,6 +232,7 @@ class FusedTrainStep:
     def step(self, clean, ldct, noise=None, t=None, context_ca=None):
         """One optimizer step on (clean, ldct) [N,C,H,W] fp32 device tensors; returns the last chunk's loss.
         ``context_ca``: cross-attention conditioning (conditioning "attention", e.g. VAE latents)."""
+        self._refuse_swapped("step")
         loss = self._fwd_bwd(clean, ldct, noise, t, context_ca)
         if self.overlap:
             self._overlapped_tail(self._bwd_bucket)
@@ -253,7 +267,8 @@ class FusedTrainStep:
     def _adamw(self):
         b1, b2 = self.hp["betas"]
         ops.adamw_sched(self.flat.data, self.flat.grad, self.m, self.v, self.step_ctr, self.hp["lr"], self.hp["warmup"],
-                        self.hp["total"], b1, b2, self.hp["eps"], self.hp["wd"], 1.0 / self.world)
+                        self.hp["total"], b1, b2, self.hp["eps"], self.hp["wd"], 1.0 / self.world, ema=self.ema,
+                        ema_decay=self.ema_decay or 0.0, ema_warmup=self.ema_warmup)
         ops.counter_add(self.step_ctr)
 
     def _fwd_bwd(self, clean, ldct, noise=None, t=None, context_ca=None):
@@ -341,6 +356,68 @@ class FusedTrainStep:
             steps = int(sched_state.get("last_epoch", 0))
         self.step_ctr.fill_(steps)
 
+    # --------------------------------------------------------------- EMA
+    def _refuse_swapped(self, what: str) -> None:
+        if self._swapped:
+            raise RuntimeError(f"FusedTrainStep.{what} inside ema_swap(): the parameter buffer holds the EMA weights")
+
+    def _need_ema(self) -> None:
+        if self.ema is None:
+            raise RuntimeError("this FusedTrainStep keeps no EMA (ema_decay=None)")
+
+    def _named_slices(self):
+        """(state_dict name, parameter, offset, numel) of every parameter, shared ones under each of their names."""
+        for name, p in self.model.named_parameters(remove_duplicate=False):
+            off, n = self.flat.offsets[id(p)]
+            yield name, p, off, n
+
+    def ema_state_dict(self) -> dict:
+        """The EMA weights as {name: cpu tensor} in ``model.state_dict()`` naming; buffers (no EMA is kept of
+        them) are taken from the model as they are."""
+        self._need_ema()
+        self._refuse_swapped("ema_state_dict")
+        ema = {name: self.ema[off:off + n].view_as(p) for name, p, off, n in self._named_slices()}
+        return {k: ema.get(k, v).detach().cpu().clone() for k, v in self.model.state_dict().items()}
+
+    def load_ema_state_dict(self, sd: dict) -> None:
+        """Inverse of ema_state_dict: the parameters' entries of ``sd`` become the EMA (buffers are ignored)."""
+        self._need_ema()
+        self._refuse_swapped("load_ema_state_dict")
+        with torch.no_grad():
+            for name, p, off, n in self._named_slices():
+                t = torch.as_tensor(sd[name])
+                if t.numel() != n:
+                    raise ValueError(f"EMA entry {name}: {tuple(t.shape)} does not fit {tuple(p.shape)}")
+                self.ema[off:off + n].copy_(t.reshape(-1))
+
+    def reset_ema(self) -> None:
+        """Restart the EMA from the current parameters."""
+        self._need_ema()
+        self._refuse_swapped("reset_ema")
+        self.ema.copy_(self.flat.data)
+
+    def _exchange_ema(self) -> None:
+        with torch.no_grad():
+            tmp = self.flat.data.clone()
+            self.flat.data.copy_(self.ema)
+            self.ema.copy_(tmp)
+        self.eng.invalidate_weights()            # bf16 kernel weights re-derived from the exchanged masters
+
+    @contextlib.contextmanager
+    def ema_swap(self):
+        """Run the model on its EMA weights: the contents of ``flat.data`` and ``self.ema`` are exchanged in place on
+        entry and exchanged back on exit (the buffers stay where they are, so a captured graph remains valid).
+        No optimizer step may run in between."""
+        self._need_ema()
+        self._refuse_swapped("ema_swap")
+        self._exchange_ema()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._swapped = False
+            self._exchange_ema()
+
     # ---------------------------------------------------------- hipGraph
     @_own_stream
     def capture(self, clean, ldct, warmup_iters: int = 2, split_collectives: Optional[bool] = None,
@@ -357,11 +434,15 @@ class FusedTrainStep:
         trace: parameters, Adam moments and the step counter are restored afterwards, so the first replay
         is optimizer step 1 with the schedule's first LR, as in the reference loop
         (flow_matching_lib.py:148-182)."""
+        self._refuse_swapped("capture")
         self._split = self.world > 1 if split_collectives is None else bool(split_collectives)
         self._static = (clean.clone(), ldct.clone() if ldct is not None else None,
                         noise.clone() if noise is not None else None, t.clone() if t is not None else None,
                         context_ca.clone() if context_ca is not None else None)
-        snap = (self.flat.data.clone(), self.m.clone(), self.v.clone(), self.step_ctr.clone(), self.loss_sum.clone())
+        live = [self.flat.data, self.m, self.v, self.step_ctr, self.loss_sum]
+        if self.ema is not None:
+            live.append(self.ema)
+        snap = [t.clone() for t in live]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -369,7 +450,7 @@ class FusedTrainStep:
                 self.step(*self._static)
         torch.cuda.current_stream().wait_stream(s)
         ops.release_combine_workspace(s)   # the warm-up stream is not used again
-        for dst, src in zip((self.flat.data, self.m, self.v, self.step_ctr, self.loss_sum), snap):
+        for dst, src in zip(live, snap):
             dst.copy_(src)
         self.flat.grad.zero_()
         del snap
@@ -397,6 +478,7 @@ class FusedTrainStep:
 
     @_own_stream
     def replay(self, clean=None, ldct=None, context_ca=None, noise=None, t=None):
+        self._refuse_swapped("replay")
         for i, new in ((0, clean), (1, ldct), (2, noise), (3, t), (4, context_ca)):
             if new is None:
                 continue

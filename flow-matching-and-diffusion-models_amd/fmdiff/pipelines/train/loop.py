@@ -16,6 +16,11 @@ differ only in the objective, checkpoint prefix and log wording).  Kept from the
   (``epoch,train_loss``), rank-0-only I/O, ``resume`` / ``training.resume``;
 * visual grids every ``save_images_every`` epochs (``decode_diffusion_batch`` of ``visual_samples`` images).
 
+Added: ``training.ema_decay`` (absent, null or 0: off) / ``training.ema_warmup`` keep an exponential moving average
+of the weights inside the AdamW launch (``FusedTrainStep(ema_decay=...)``); the checkpoints then carry it under one
+more key, ``"ema"`` (the reference's loaders read ``payload["model"]`` and ignore it), and the visual grids are
+sampled from it.
+
 Changed, MI355X-first: the step is ``FusedTrainStep`` (HIP UNet forward/backward, fused AdamW +
 cosine LR on the device, gradients all-reduced over RCCL -- the reference has no gradient sync, SURVEY
 §0.4), replayed from a hipGraph for full batches; the epoch loss accumulates on the device (no per-chunk
@@ -23,6 +28,7 @@ cosine LR on the device, gradients all-reduced over RCCL -- the reference has no
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import math
 from pathlib import Path
@@ -109,6 +115,7 @@ def _train_loop(dataset, val_dataset, resume, cfg, tr, mblock, objective, step_f
     grad_accum = max(1, int(tr.get("gradient_accumulation_steps", 1)))
     warmup = int(tr.get("lr_warmup_steps", 500))
     latent_norm = tr.get("latent_norm")
+    ema_decay, ema_warmup = U.resolve_ema(tr)
 
     base_out = Path(tr.get("output_dir", default_out))
     out_dir = _broadcast_path(U.allocate_run_dir(base_out) if (resume is None and U.is_main_process())
@@ -124,10 +131,11 @@ def _train_loop(dataset, val_dataset, resume, cfg, tr, mblock, objective, step_f
     n_train = int(scheduler.config.num_train_timesteps)
     total_steps = epochs * math.ceil(len(dataset) / batch_size)
     make = step_factory or default_step_factory
+    ema_kw = dict(ema_decay=ema_decay, ema_warmup=ema_warmup) if ema_decay is not None else {}
     step = make(model, objective=objective, lr=lr, weight_decay=weight_decay, warmup=warmup, total_steps=total_steps,
                 num_train_timesteps=n_train, grad_accum=grad_accum,
                 ddpm_scheduler=scheduler if objective == "ddpm" else None,
-                process_group=dist.group.WORLD if U.is_distributed() else None)
+                process_group=dist.group.WORLD if U.is_distributed() else None, **ema_kw)
 
     sampler = DistributedSampler(dataset, shuffle=True) if U.is_distributed() else None
     loader = DataLoader(dataset, batch_size=batch_size, shuffle=sampler is None, sampler=sampler,
@@ -194,6 +202,8 @@ def _train_loop(dataset, val_dataset, resume, cfg, tr, mblock, objective, step_f
         state = {"model": {k: v.detach().cpu() for k, v in model.state_dict().items()},
                  "optimizer": step.optimizer_state_dict(), "lr_scheduler": step.lr_scheduler_state_dict(),
                  "scaler": None, "epoch": epoch, "best_metric": best}
+        if ema_decay is not None:
+            state["ema"] = step.ema_state_dict()
         if U.is_main_process():
             U.save_checkpoint(state, out_dir / f"{prefix}_last.pt")
             if avg < best:
@@ -207,7 +217,7 @@ def _train_loop(dataset, val_dataset, resume, cfg, tr, mblock, objective, step_f
 
         if vis_on and U.is_main_process() and vis_t is not None and (epoch % vis_every == 0 or epoch == epochs):
             model.eval()
-            with torch.no_grad():
+            with torch.no_grad(), (step.ema_swap() if ema_decay is not None else contextlib.nullcontext()):
                 outs = decode_diffusion_batch(model, tr, mblock, device, tuple(vis_t.shape),
                                               vis_c if mode in {"concatenate", "attention"} else None)
             vis_dir = out_dir / "visuals"

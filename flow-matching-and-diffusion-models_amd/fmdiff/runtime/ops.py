@@ -1412,9 +1412,19 @@ def mse(pred_nhwc, ta, tb, tb_sign, grad_scale, loss, partial, dpred=None):
 
 
 def adamw_sched(p, g, m, v, step_ctr, base_lr, warmup, total, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0,
-                grad_scale=1.0):
-    _lib.call("fmd_adamw_sched", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(step_ctr), float(base_lr), int(warmup),
-              int(total), float(beta1), float(beta2), float(eps), float(wd), float(grad_scale), stream())
+                grad_scale=1.0, ema=None, ema_decay=0.0, ema_warmup=True):
+    """``ema``: a flat fp32 buffer like ``p``; then the same launch also moves it towards the new parameters
+    (fmd_adamw_sched_ema, decay ``ema_decay`` in [0, 1), warmed up as min(decay, (1 + s) / (10 + s)) if
+    ``ema_warmup``)."""
+    if ema is None:
+        _lib.call("fmd_adamw_sched", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(step_ctr), float(base_lr), int(warmup),
+                  int(total), float(beta1), float(beta2), float(eps), float(wd), float(grad_scale), stream())
+        return
+    if ema.dtype != F32 or not ema.is_contiguous() or ema.numel() != p.numel() or ema.device != p.device:
+        raise ValueError("adamw_sched: ema must be a contiguous fp32 buffer of p's size on p's device")
+    _lib.call("fmd_adamw_sched_ema", _p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(step_ctr), float(base_lr),
+              int(warmup), int(total), float(beta1), float(beta2), float(eps), float(wd), float(grad_scale),
+              float(ema_decay), int(bool(ema_warmup)), stream())
 
 
 def counter_add(ctr, v=1):

@@ -78,24 +78,32 @@ def _load_legacy_unet_state(model: torch.nn.Module, state: Dict[str, torch.Tenso
                            "Architecture/config likely differs from the source checkpoint.")
 
 
-def _read_state(ckpt_path: str, device) -> Dict[str, torch.Tensor]:
+def _read_state(ckpt_path: str, device, use_ema: bool = False) -> Dict[str, torch.Tensor]:
+    """The checkpoint's weights; ``use_ema``: its ``"ema"`` entry (a trainer run with ``training.ema_decay``)."""
     if ckpt_path.endswith(".safetensors"):
+        if use_ema:
+            raise KeyError(f"checkpoint {ckpt_path} has no 'ema' entry (a safetensors file holds one set of weights)")
         from safetensors.torch import load_file
         return load_file(ckpt_path, device="cpu")
     payload = torch.load(ckpt_path, map_location="cpu", weights_only=True)
+    if use_ema:
+        if not isinstance(payload, dict) or not payload.get("ema"):
+            raise KeyError(f"checkpoint {ckpt_path} has no 'ema' entry (was it trained with training.ema_decay?)")
+        return payload["ema"]
     return payload["model"] if isinstance(payload, dict) and "model" in payload else payload
 
 
-def build_diffusion_model(cfg: dict, device, ckpt_path=None, set_eval: bool = True):
+def build_diffusion_model(cfg: dict, device, ckpt_path=None, set_eval: bool = True, use_ema: bool = False):
     """UNet of ``cfg["model"]["unet"]`` (conditioning from the training block, channels =
-    ``training.channels`` or ``unet.out_channels`` or 1) on ``device``, optionally loaded from a checkpoint."""
+    ``training.channels`` or ``unet.out_channels`` or 1) on ``device``, optionally loaded from a checkpoint;
+    ``use_ema``: from the checkpoint's EMA weights (``"ema"``) in place of ``"model"``."""
     tr = cfg["training"]
     unet_cfg = cfg["model"].get("unet", {})
     mode = resolve_conditioning_mode(tr.get("conditioning") or cfg["model"].get("conditioning"))
     channels = int(tr.get("channels", unet_cfg.get("out_channels", 1)) or 1)
     model = DiffusionUNetFactory().build(unet_cfg, mode, channels).to(device)
     if ckpt_path is not None:
-        state = _read_state(str(ckpt_path), device)
+        state = _read_state(str(ckpt_path), device, use_ema)
         strict = bool(unet_cfg.get("legacy_strict_shapes", True))
         if bool(unet_cfg.get("load_legacy", False)):
             _load_legacy_unet_state(model, state, strict_shapes=strict)

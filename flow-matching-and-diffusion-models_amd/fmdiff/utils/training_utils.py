@@ -23,7 +23,7 @@ import torch
 import torch.distributed as dist
 
 __all__ = ["load_json_config", "save_json_config", "allocate_run_dir", "set_seed", "resolve_device",
-           "resolve_batch_size", "save_checkpoint", "latest_checkpoint", "maybe_load_checkpoint", "setup_distributed",
+           "resolve_batch_size", "resolve_ema", "save_checkpoint", "latest_checkpoint", "maybe_load_checkpoint", "setup_distributed",
            "is_distributed", "is_main_process", "get_rank", "get_world_size"]
 
 
@@ -83,6 +83,20 @@ def resolve_batch_size(training_cfg: dict, key: str, fallback) -> int:
     return int(value)
 
 
+def resolve_ema(training_cfg: dict) -> Tuple[Optional[float], bool]:
+    """(``training.ema_decay``, ``training.ema_warmup``): the decay is None (EMA off) when the key is absent, null
+    or 0; the warm-up flag defaults to true."""
+    value = training_cfg.get("ema_decay")
+    if value is None or (isinstance(value, str) and value.lower() == "none"):
+        return None, bool(training_cfg.get("ema_warmup", True))
+    decay = float(value)
+    if decay == 0.0:
+        decay = None
+    elif not 0.0 < decay < 1.0:
+        raise ValueError(f"training.ema_decay must lie in [0, 1), got {value!r}")
+    return decay, bool(training_cfg.get("ema_warmup", True))
+
+
 def save_checkpoint(state: dict, path) -> None:
     """Write ``state`` with torch.save (atomic: temporary file + rename, so a crash never leaves half a file)."""
     path = Path(path)
@@ -138,7 +152,8 @@ def maybe_load_checkpoint(path, prefix: str, model, optimizer=None, scheduler=No
 
     ``optimizer`` may be a fused train step (anything with ``load_optimizer_state_dict``): then the AdamW
     moments and the step count come from the checkpoint's torch-format ``optimizer`` / ``lr_scheduler``
-    entries, whichever trainer wrote them."""
+    entries, whichever trainer wrote them.  A step that keeps an EMA of the weights (``step.ema``) takes it from the
+    checkpoint's ``ema`` entry; from a checkpoint without one its EMA restarts from the loaded parameters."""
     if path is None:
         return 1, float("inf")
     path = Path(path)
@@ -152,6 +167,13 @@ def maybe_load_checkpoint(path, prefix: str, model, optimizer=None, scheduler=No
             optimizer.load_optimizer_state_dict(payload["optimizer"], payload.get("lr_scheduler"))
         else:
             optimizer.load_state_dict(payload["optimizer"])
+    if getattr(optimizer, "ema", None) is not None:
+        if payload.get("ema"):
+            optimizer.load_ema_state_dict(payload["ema"])
+        else:
+            logging.warning("%s checkpoint %s has no 'ema' entry: the EMA restarts from the loaded parameters",
+                            prefix, path)
+            optimizer.reset_ema()
     if scheduler is not None and payload.get("lr_scheduler"):
         scheduler.load_state_dict(payload["lr_scheduler"])
     if scaler is not None and payload.get("scaler"):

@@ -584,6 +584,16 @@ int fmd_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr,
 int fmd_adamw_sched(float* p, const float* g, float* m, float* v, int64_t n, const int32_t* step_ctr, float base_lr,
                     int32_t warmup, int32_t total, float beta1, float beta2, float eps, float wd, float grad_scale,
                     fmd_stream_t s);
+/* fmd_adamw_sched plus, in the same pass, an exponential moving average of the parameters (ema: a fifth flat fp32
+ * buffer of n elements).  With s = step_ctr[0] (0-based, the s of the LR schedule):
+ *   d   = ema_warmup ? min(ema_decay, (1 + s) / (10 + s)) : ema_decay
+ *   ema = ema + (1 - d) * (p_new - ema)
+ * p_new is the parameter this launch has just computed.  Every operation is one rounded fp32 operation (division,
+ * subtraction, multiply, add; none contracted), so separate fp32 ops on the host reproduce the bits.  p, m, v are
+ * written exactly as by fmd_adamw_sched.  Returns -1 for a NULL ema or ema_decay outside [0, 1). */
+int fmd_adamw_sched_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const int32_t* step_ctr,
+                        float base_lr, int32_t warmup, int32_t total, float beta1, float beta2, float eps, float wd,
+                        float grad_scale, float ema_decay, int32_t ema_warmup, fmd_stream_t s);
 int fmd_flow_euler(float* x, const float* v, int32_t Kpad, const float* sigmas, const int32_t* index, int32_t N,
                    int32_t Cx, int32_t HW, const float* cond, int32_t Cc, int32_t Cpad, void* next, fmd_stream_t s);
 /* noise: DDPM variance noise, a per-step table whose row 0 belongs to step noise_base (row = index - noise_base),
