@@ -29,18 +29,6 @@ namespace {
 constexpr int BN_ROWS = FMD_BN_ROWS;   // rows of one partial-sum block of the backward (as fmd_channel_stats: 64)
 static_assert(BN_ROWS % 32 == 0, "32 row lanes per block");
 
-FMD_DEV void unpack8(const u32x4& q, float (&v)[8]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[2 * j] = bf_lo(q[j]);
-    v[2 * j + 1] = bf_hi(q[j]);
-  }
-}
-
-FMD_DEV u32x4 pack8(const float (&v)[8]) {
-  return u32x4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
-}
-
 // The 8 channels of group ``idx8`` of x: bf16 (one 16-byte load) or fp32 (two).
 template <bool XF32>
 FMD_DEV void load8(const void* x, size_t idx8, float (&v)[8]) {
@@ -52,16 +40,6 @@ FMD_DEV void load8(const void* x, size_t idx8, float (&v)[8]) {
   } else {
     unpack8(*(const u32x4*)((const bf16r*)x + idx8 * 8), v);
   }
-}
-
-// v as two bf16 terms: hi = bf16(v), lo = bf16(v - hi); hi + lo carries about 16 significant bits of v
-FMD_DEV void split8(const float (&v)[8], u32x4& hi, u32x4& lo) {
-  hi = pack8(v);
-  float h[8], l[8];
-  unpack8(hi, h);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) l[j] = v[j] - h[j];
-  lo = pack8(l);
 }
 
 // Sum over the rows of a [rows][C][2] fp32 slab for the 8 channels c0 .. c0+7 of this workgroup, in fp64: thread

@@ -11,6 +11,7 @@
 typedef uint16_t bf16r;                                           // raw bf16 bits in memory
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;        // MFMA A/B fragment (4 VGPR)
 typedef __attribute__((ext_vector_type(4))) float f32x4;          // MFMA 16x16 accumulator
+typedef __attribute__((ext_vector_type(16))) float f32x16;        // MFMA 32x32 accumulator
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;   // 16-byte vector
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;   // 8-byte vector
 typedef __attribute__((ext_vector_type(4))) short s16x4;          // ds_read_tr16_b64 result
@@ -32,6 +33,29 @@ FMD_DEV unsigned int pack2(float lo, float hi) {
   return __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2_{lo, hi}, bf16x2_));
 }
 
+// 8 bf16 channels (one 16-byte vector) <-> 8 floats
+FMD_DEV void unpack8(const u32x4& q, float (&v)[8]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    v[2 * j] = bf_lo(q[j]);
+    v[2 * j + 1] = bf_hi(q[j]);
+  }
+}
+
+FMD_DEV u32x4 pack8(const float (&v)[8]) {
+  return u32x4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
+}
+
+// v as two bf16 terms: hi = bf16(v), lo = bf16(v - hi); hi + lo carries about 16 significant bits of v
+FMD_DEV void split8(const float (&v)[8], u32x4& hi, u32x4& lo) {
+  hi = pack8(v);
+  float h[8], l[8];
+  unpack8(hi, h);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) l[j] = v[j] - h[j];
+  lo = pack8(l);
+}
+
 // v_exp_f32 + v_rcp_f32 (1 ulp): no IEEE division sequence in the hot prologues
 FMD_DEV float sigmoidf_(float z) { return __builtin_amdgcn_rcpf(1.0f + __expf(-z)); }
 FMD_DEV float siluf_(float z) { return z * sigmoidf_(z); }
@@ -43,6 +67,9 @@ FMD_DEV float silu_grad(float z) {
 
 FMD_DEV f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+FMD_DEV f32x16 mfma32(const bf16x8& a, const bf16x8& b, const f32x16& c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
@@ -67,6 +94,28 @@ FMD_DEV float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+
+FMD_DEV double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// 256 threads: butterfly per wave, then the four wave totals in order; every thread returns the sum.
+// red: 4 doubles of LDS.
+FMD_DEV double block_sum(double v, double* red) {
+  v = wave_sum_f64(v);
+  const int tid = threadIdx.x;
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// [rows][128] bf16 LDS tile (256-B rows) with an 8-byte unit swizzle: conflict-free transposed reads
+// (ds_read_tr16) for the 4-row blocks rows {8g+q} read by one instruction.  tile128_off: the bf16-element offset
+// of 8-byte unit ``unit`` of row ``row``.
+FMD_DEV int tile128_swz(int row) { return 4 * ((row & 3) | (((row >> 3) & 1) << 2)); }
+FMD_DEV int tile128_off(int row, int unit) { return row * 128 + 4 * (unit ^ tile128_swz(row)); }
 
 // XCD-aware bijective block remap: blocks b, b+8, ... share one XCD's L2; give
 // each XCD a contiguous range of the logical grid (cdna_hip_programming.md T1).

@@ -23,8 +23,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 constexpr int NT9 = 256;
 constexpr int TH = 16, TW = 16, BCO = 128, BK = 32, KC = BK / 8;
 constexpr int WTILE = KC * BCO * 16;   // bytes of one tap's weight tile (8 KiB)
@@ -50,10 +48,6 @@ struct G9 {
   static constexpr int NR = (NPIECE + NT9 - 1) / NT9;              // staging rounds per chunk (6 | 2)
   static_assert(NR <= 6 && NR * NT9 >= NPIECE, "staging rounds");
 };
-
-FMD_DEV f32x16 mfma32(const bf16x8& a, const bf16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
 
 FMD_DEV bf16x8 as_bf16x8(const u32x4& u) { return __builtin_bit_cast(bf16x8, u); }
 #ifndef FMD_H9_FENCE

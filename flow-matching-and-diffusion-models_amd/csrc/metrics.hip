@@ -44,12 +44,6 @@ struct Mom {
   double x, y, xx, yy, xy;
 };
 
-FMD_DEV double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // torch.clamp(v, 0, 1): both comparisons are false for a NaN, which therefore passes through
 FMD_DEV float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
 

@@ -28,28 +28,6 @@
 
 namespace {
 
-FMD_DEV void unpack8(const u32x4& q, float (&v)[8]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[2 * j] = bf_lo(q[j]);
-    v[2 * j + 1] = bf_hi(q[j]);
-  }
-}
-
-FMD_DEV u32x4 pack8(const float (&v)[8]) {
-  return u32x4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
-}
-
-// v as two bf16 terms: hi = bf16(v), lo = bf16(v - hi) (csrc/batchnorm.hip split8)
-FMD_DEV void split8(const float (&v)[8], u32x4& hi, u32x4& lo) {
-  hi = pack8(v);
-  float h[8], l[8];
-  unpack8(hi, h);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) l[j] = v[j] - h[j];
-  lo = pack8(l);
-}
-
 FMD_DEV void load8f(const float* p, float (&v)[8]) {
   const f32x4 q0 = ((const f32x4*)p)[0], q1 = ((const f32x4*)p)[1];
 #pragma unroll
@@ -185,21 +163,6 @@ __global__ __launch_bounds__(256) void perc_stage_bwd_kernel(const bf16r* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------- tap
-FMD_DEV double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// 256 threads: butterfly per wave, then the four wave totals in order
-FMD_DEV double block_sum(double v, double* red) {
-  v = wave_sum_f64(v);
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 struct TapArgs {
   const float* y;      // fwd: [2 N][H][W][Cp]; bwd: the recon rows [N][H][W][Cp]
   int N, H, W, Cp, C, pool;

@@ -22,12 +22,6 @@ constexpr int PW_ROWS = FMD_POINTWISE_ROWS;   // rows per workgroup: 256 threads
 constexpr int PW_MAXC = FMD_POINTWISE_MAXC;
 static_assert(PW_ROWS % 256 == 0 && PW_MAXC == 8, "trip count; a row of 8 bf16 is one 16-byte load");
 
-FMD_DEV double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 struct PwArgs {
   const bf16r* dy;   // [M][ldy]
   const bf16r* x;    // [M][ldx]

@@ -6,7 +6,7 @@
 //      arithmetic of fmd_conv_gn_apply (conv_igemm<128, 128, 2, 2, 32, true>, csrc/conv.hip) with the same MFMA,
 //      the same k order over Kd and the same rounding, so dx is bit-identical to that launch;
 //   2. accumulates dW_s[Kd][c-tile] += dy_tile^T . x_tile in registers: both operands are pixel-major, so the
-//      fragments come from the SAME LDS images as (1) through ds_read_b64_tr_b16 (the layout of csrc/wgrad.hip:
+//      fragments come from the SAME LDS images as (1) through ds_read_b64_tr_b16 (csrc/wgrad.hip's layout, tile128_off:
 //      its 8-byte swizzle keeps 16-byte chunks whole, so the row reads of (1) work on it too);
 //   3. (c-tile 0 only) accumulates db_s[k] += sum_p dy[p][k].
 // At the end each workgroup writes its fp32 partial slab; fmd_wgrad_combine (wgrad_reduce2, T = 1) sums the slabs
@@ -32,10 +32,6 @@ struct SArgs {
   int nsl;        // slabs: min(G, ntp) -- a group without tiles writes none
   int xcd;        // G % 8 == 0: the c-tiles of a pixel group run on one XCD (dy shared through its L2)
 };
-
-// [pixel][128] bf16 tile in the layout of csrc/wgrad.hip: 8-byte unit swizzle, conflict-free transposed reads
-FMD_DEV int swz(int row) { return 4 * ((row & 3) | (((row >> 3) & 1) << 2)); }
-FMD_DEV int toff(int row, int unit) { return row * 128 + 4 * (unit ^ swz(row)); }   // in bf16 elements
 
 __global__ __launch_bounds__(NT, 2) void skip_bwd_kernel(const SArgs A) {
   __shared__ __attribute__((aligned(16))) bf16r ldsW[CT * KD];    // W_s^T[c][k], 16-byte chunk ^ (c & 15)
@@ -117,8 +113,8 @@ __global__ __launch_bounds__(NT, 2) void skip_bwd_kernel(const SArgs A) {
   // transposed fragment of a [pixel][128] tile: pixels 32 st + 8 lg + {q, 4 + q}, columns col0 + 4 pp
   const int lg = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
   auto frag = [&](const bf16r* t, int st, int col0) -> bf16x8 {
-    const s16x4 lo = ds_read_tr16(t + toff(32 * st + 8 * lg + q, col0 / 4 + pp));
-    const s16x4 hi = ds_read_tr16(t + toff(32 * st + 8 * lg + 4 + q, col0 / 4 + pp));
+    const s16x4 lo = ds_read_tr16(t + tile128_off(32 * st + 8 * lg + q, col0 / 4 + pp));
+    const s16x4 hi = ds_read_tr16(t + tile128_off(32 * st + 8 * lg + 4 + q, col0 / 4 + pp));
     typedef __attribute__((ext_vector_type(8))) short s16x8;
     s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bf16x8, v);
@@ -133,8 +129,8 @@ __global__ __launch_bounds__(NT, 2) void skip_bwd_kernel(const SArgs A) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int r = rb + 16 * j;
-      *(u32x4*)(ldsY + toff(r, 2 * chunk)) = ry[j];
-      *(u32x4*)(ldsX + toff(r, 2 * chunk)) = rx[j];
+      *(u32x4*)(ldsY + tile128_off(r, 2 * chunk)) = ry[j];
+      *(u32x4*)(ldsX + tile128_off(r, 2 * chunk)) = rx[j];
     }
     if (do_bias) {
 #pragma unroll
@@ -166,7 +162,7 @@ __global__ __launch_bounds__(NT, 2) void skip_bwd_kernel(const SArgs A) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int r = wn * 32 + 16 * j + l16;
-        bfr[j] = *(const bf16x8*)(ldsY + toff(r, 2 * kc));
+        bfr[j] = *(const bf16x8*)(ldsY + tile128_off(r, 2 * kc));
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -213,7 +209,7 @@ __global__ __launch_bounds__(NT, 2) void skip_bwd_kernel(const SArgs A) {
         if (p >= A.M) continue;
         const int n = p / A.HW;
         const u32x4 ve = *(const u32x4*)(ldsY + pi * CT + ((chunk ^ (pi & 15)) * 8));
-        const u32x4 vx = *(const u32x4*)(ldsX + toff(pi, 2 * chunk));
+        const u32x4 vx = *(const u32x4*)(ldsX + tile128_off(pi, 2 * chunk));
         const float* pq = g.P + (size_t)n * C + co;
         const float* qq = g.Q + (size_t)n * C + co;
         const float* rr = g.R + (size_t)n * C + co;

@@ -27,21 +27,6 @@ static_assert(VL_CHUNK % 1024 == 0 && VL_ROWS % 256 == 0 && GS_ROWS == 256, "tri
 
 enum { T_L1, T_MSE, T_BCE, T_FOCAL, T_BCE_FOCAL, T_HINGE_REAL, T_HINGE_FAKE, T_NEG, T_SQUARE, T_COUNT };
 
-FMD_DEV double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// 256 threads: butterfly per wave, then the four wave totals in order; every thread returns the sum.
-FMD_DEV double block_sum(double v, double* red) {
-  v = wave_sum_f64(v);
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // v: the term, u: d term / d x, both fp64.  Comparisons with a NaN are false: a NaN x gives a NaN term.
 template <int T>
 FMD_DEV void term_of(float xf, float tf, double alpha, double& v, double& u) {

@@ -16,8 +16,6 @@
 
 #include <math.h>
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 namespace {
 
 constexpr int VQ_BM = 64;          // latent vectors per workgroup: two 32-column MFMA tiles
@@ -28,10 +26,6 @@ constexpr int VQ_DMAX = 256;
 constexpr int VQ_TARGET_WG = 512;  // two workgroups per CU
 constexpr int VQ_MAX_SPLITS = 64;
 constexpr int VQ_FROWS = 32;       // latent vectors per finalize workgroup
-
-FMD_DEV f32x16 mfma32(const bf16x8& a, const bf16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
 
 FMD_DEV bf16x8 ld8(const bf16r* p) { return __builtin_bit_cast(bf16x8, *(const u32x4*)p); }
 

@@ -26,11 +26,6 @@ struct WArgs {
                 // 3-D input conv with 27 taps x 8 channels = 2 tiles instead of 27 tiles of 8 valid columns)
 };
 
-// 8-byte unit swizzle for the [32][128] bf16 tile (256-B rows): conflict-free
-// transposed reads for the 4-row blocks rows {8g+q} read by one instruction.
-FMD_DEV int swz(int row) { return 4 * ((row & 3) | (((row >> 3) & 1) << 2)); }
-FMD_DEV int lds_off(int row, int unit) { return row * 128 + 4 * (unit ^ swz(row)); }  // in bf16 elements
-
 // bx = (co tile, tap, ci tile) index, split of nsplit: a single launch's blockIdx.x, blockIdx.y of gridDim.y
 FMD_DEV void wgrad_body(const WArgs& A, int bx, const int split, const int nsplit) {
   __shared__ __attribute__((aligned(16))) bf16r lds[2][2][BKP * 128];
@@ -151,8 +146,8 @@ FMD_DEV void wgrad_body(const WArgs& A, int bx, const int split, const int nspli
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int r = rb + 16 * j;
-      *(u32x4*)(&lds[buf][0][lds_off(r, 2 * chunk)]) = ry[j];
-      *(u32x4*)(&lds[buf][1][lds_off(r, 2 * chunk)]) = rg[j];
+      *(u32x4*)(&lds[buf][0][tile128_off(r, 2 * chunk)]) = ry[j];
+      *(u32x4*)(&lds[buf][1][tile128_off(r, 2 * chunk)]) = rg[j];
     }
   };
 
@@ -165,8 +160,8 @@ FMD_DEV void wgrad_body(const WArgs& A, int bx, const int split, const int nspli
   const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
   auto frag = [&](const bf16r* t, int col0) -> bf16x8 {
     // rows 8g+q (first) and 8g+4+q (second); cols col0 + 4pp
-    const s16x4 lo = ds_read_tr16(t + lds_off(8 * g + q, col0 / 4 + pp));
-    const s16x4 hi = ds_read_tr16(t + lds_off(8 * g + 4 + q, col0 / 4 + pp));
+    const s16x4 lo = ds_read_tr16(t + tile128_off(8 * g + q, col0 / 4 + pp));
+    const s16x4 hi = ds_read_tr16(t + tile128_off(8 * g + 4 + q, col0 / 4 + pp));
     typedef __attribute__((ext_vector_type(8))) short s16x8;
     s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bf16x8, v);

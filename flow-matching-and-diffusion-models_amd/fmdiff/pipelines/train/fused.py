@@ -72,21 +72,23 @@ def _own_stream(fn):
 
 
 class FlatParams:
-    """Re-point every parameter (and its .grad) into one flat fp32 buffer.  ``first``: parameters laid out
-    at the front (``split_at`` elements), e.g. those whose gradients are final early in the backward."""
+    """Re-point every parameter (and its .grad) into one flat fp32 buffer, with the Adam moments ``m`` / ``v``
+    laid out like it.  ``first``: parameters laid out at the front (``split_at`` elements), e.g. those whose
+    gradients are final early in the backward.  ``adamw_state_dict`` / ``load_adamw_state_dict`` are the one place
+    where the ``torch.optim.AdamW.state_dict()`` format is spelled out."""
 
     def __init__(self, model: torch.nn.Module, first=None):
-        params = [p for p in model.parameters()]
+        self.params = params = [p for p in model.parameters()]   # torch's order: the keys of the optimizer state
         if first:
             ids = {id(p) for p in first}
             params = list(first) + [p for p in params if id(p) not in ids]
         self.split_at = sum(p.numel() for p in first) if first else 0
-        self.order = params
         dev = params[0].device
         total = sum(p.numel() for p in params)
         self.data = torch.empty(total, device=dev, dtype=torch.float32)
         self.grad = torch.zeros(total, device=dev, dtype=torch.float32)
-        self.slices = []
+        self.m = torch.zeros_like(self.data)
+        self.v = torch.zeros_like(self.data)
         self.offsets = {}           # id(param) -> (offset, numel) in the flat buffers
         off = 0
         with torch.no_grad():
@@ -95,10 +97,48 @@ class FlatParams:
                 self.data[off:off + n].copy_(p.detach().reshape(-1))
                 p.data = self.data[off:off + n].view_as(p)
                 p.grad = self.grad[off:off + n].view_as(p)
-                self.slices.append((off, n))
                 self.offsets[id(p)] = (off, n)
                 off += n
         self.numel = total
+
+    def _moments(self):
+        """(index in ``model.parameters()``, m view, v view), the views shaped like the parameter."""
+        for i, p in enumerate(self.params):
+            off, n = self.offsets[id(p)]
+            yield i, self.m[off:off + n].view_as(p), self.v[off:off + n].view_as(p)
+
+    def adamw_state_dict(self, step: int, *, lr, betas, eps, weight_decay, **extra) -> dict:
+        """The moments after ``step`` optimizer steps as a ``torch.optim.AdamW.state_dict()``: state keyed by the
+        index in ``model.parameters()`` (empty before the first step, as torch's is), one param group.  ``extra``:
+        further group keys (``initial_lr``)."""
+        state = {}
+        if step > 0:
+            for i, m, v in self._moments():
+                state[i] = {"step": torch.tensor(float(step)), "exp_avg": m.detach().cpu().clone(),
+                            "exp_avg_sq": v.detach().cpu().clone()}
+        group = {"lr": lr, "betas": betas, "eps": eps, "weight_decay": weight_decay, "amsgrad": False,
+                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                 "decoupled_weight_decay": True, **extra, "params": list(range(len(self.params)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_adamw_state_dict(self, sd: Optional[dict]) -> int:
+        """Inverse of ``adamw_state_dict`` (also takes a genuine torch AdamW state of the same module; integer or
+        string keys).  Returns the step count: the largest ``step`` of the entries, 0 without any.  The moments
+        are zeroed first, so a parameter without an entry ends with zero moments, which is what torch means by a
+        parameter without state."""
+        st = sd.get("state", {}) if sd else {}
+        steps = 0
+        with torch.no_grad():
+            self.m.zero_()
+            self.v.zero_()
+            for i, m, v in self._moments():
+                e = st.get(i) if i in st else st.get(str(i))
+                if not e:
+                    continue
+                m.copy_(torch.as_tensor(e["exp_avg"]).reshape(m.shape))
+                v.copy_(torch.as_tensor(e["exp_avg_sq"]).reshape(v.shape))
+                steps = max(steps, int(float(torch.as_tensor(e["step"]))))
+        return steps
 
 
 def _segment_buckets(sizes, buckets: int):
@@ -157,9 +197,8 @@ class FusedTrainStep:
             first = [p for g in groups for p in g]
             self.seg_buckets = _segment_buckets([sum(p.numel() for p in g) for g in groups], allreduce_buckets)
         self.flat = FlatParams(model, first)
+        self.m, self.v = self.flat.m, self.flat.v   # the same tensors: the flat object owns them
         dev = self.flat.data.device
-        self.m = torch.zeros_like(self.flat.data)
-        self.v = torch.zeros_like(self.flat.data)
         if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
         self.ema_decay = None if ema_decay is None else float(ema_decay)
@@ -266,8 +305,9 @@ class FusedTrainStep:
 
     def _adamw(self):
         b1, b2 = self.hp["betas"]
-        ops.adamw_sched(self.flat.data, self.flat.grad, self.m, self.v, self.step_ctr, self.hp["lr"], self.hp["warmup"],
-                        self.hp["total"], b1, b2, self.hp["eps"], self.hp["wd"], 1.0 / self.world, ema=self.ema,
+        f = self.flat
+        ops.adamw_sched(f.data, f.grad, self.m, self.v, self.step_ctr, self.hp["lr"], self.hp["warmup"], self.hp["total"],
+                        b1, b2, self.hp["eps"], self.hp["wd"], 1.0 / self.world, ema=self.ema,
                         ema_decay=self.ema_decay or 0.0, ema_warmup=self.ema_warmup)
         ops.counter_add(self.step_ctr)
 
@@ -316,19 +356,8 @@ class FusedTrainStep:
         """The step's AdamW state in ``torch.optim.AdamW.state_dict()`` form (state keyed by the index in
         ``model.parameters()``), so a checkpoint written here resumes the reference's optimizer and back."""
         s = self.steps_done()
-        b1, b2 = self.hp["betas"]
-        state = {}
-        params = list(self.model.parameters())
-        if s > 0:
-            for i, p in enumerate(params):
-                off, n = self.flat.offsets[id(p)]
-                state[i] = {"step": torch.tensor(float(s)), "exp_avg": self.m[off:off + n].view_as(p).detach().cpu().clone(),
-                            "exp_avg_sq": self.v[off:off + n].view_as(p).detach().cpu().clone()}
-        group = {"lr": self.hp["lr"] * self.lr_multiplier(s), "betas": (b1, b2), "eps": self.hp["eps"],
-                 "weight_decay": self.hp["wd"], "amsgrad": False, "maximize": False, "foreach": None,
-                 "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": True,
-                 "initial_lr": self.hp["lr"], "params": list(range(len(params)))}
-        return {"state": state, "param_groups": [group]}
+        return self.flat.adamw_state_dict(s, lr=self.hp["lr"] * self.lr_multiplier(s), betas=tuple(self.hp["betas"]),
+                                          eps=self.hp["eps"], weight_decay=self.hp["wd"], initial_lr=self.hp["lr"])
 
     def lr_scheduler_state_dict(self) -> dict:
         """``LambdaLR`` state of get_cosine_schedule_with_warmup after the steps taken."""
@@ -339,19 +368,10 @@ class FusedTrainStep:
 
     def load_optimizer_state_dict(self, opt_state: dict, sched_state: Optional[dict] = None) -> None:
         """Inverse of optimizer_state_dict (also accepts a torch AdamW checkpoint of the reference).  The step
-        count comes from the optimizer state (else the LR scheduler's ``last_epoch``)."""
-        params = list(self.model.parameters())
-        st = opt_state.get("state", {}) if opt_state else {}
-        steps = 0
-        with torch.no_grad():
-            for i, p in enumerate(params):
-                e = st.get(i) if i in st else st.get(str(i))
-                if not e:
-                    continue
-                off, n = self.flat.offsets[id(p)]
-                self.m[off:off + n].copy_(torch.as_tensor(e["exp_avg"]).reshape(-1))
-                self.v[off:off + n].copy_(torch.as_tensor(e["exp_avg_sq"]).reshape(-1))
-                steps = max(steps, int(float(torch.as_tensor(e["step"]))))
+        count comes from the optimizer state (else the LR scheduler's ``last_epoch``).  The moments are zeroed
+        first (``FlatParams.load_adamw_state_dict``): a parameter without an entry ends with zero moments even if
+        this object has stepped before."""
+        steps = self.flat.load_adamw_state_dict(opt_state)
         if steps == 0 and sched_state:
             steps = int(sched_state.get("last_epoch", 0))
         self.step_ctr.fill_(steps)

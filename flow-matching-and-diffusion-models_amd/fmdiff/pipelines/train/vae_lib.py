@@ -166,7 +166,8 @@ class VAETrainStep:
     laid out behind the trained parameters and the AdamW launch stops short of it), so it stays bit-identical for
     any ``weight_decay``.
 
-    Parameters, gradients and Adam moments are flat fp32 buffers (``FlatParams``), the optimizer is one
+    Parameters, gradients and Adam moments are flat fp32 buffers, all owned by ``FlatParams`` (``flat``, and
+    ``disc_flat`` for the discriminator), which also writes and reads the torch optimizer state; the optimizer is one
     ``ops.adamw`` launch, and because it writes the parameters through raw pointers the step then re-derives the
     engine's bf16 weight layouts and the folded quant_conv.  ``global_step`` is a host integer used for
     ``kl_scale`` and Adam's bias correction only; nothing in ``step`` synchronises with the host."""
@@ -209,8 +210,7 @@ class VAETrainStep:
         ids = {id(p) for p in frozen}
         self.flat = FlatParams(model, first=[p for p in model.parameters() if id(p) not in ids] if frozen else None)
         self.n_trained = self.flat.split_at if frozen else self.flat.numel
-        self.m = torch.zeros_like(self.flat.data)
-        self.v = torch.zeros_like(self.flat.data)
+        self.m, self.v = self.flat.m, self.flat.v   # the same tensors: the flat object owns them
         self.global_step = 0
         self.eng.invalidate_weights()   # the parameters moved into the flat buffer
         self.disc = discriminator
@@ -224,8 +224,7 @@ class VAETrainStep:
             discriminator.train()          # as the reference's loop does at the start of every epoch
             self.disc_eng = get_disc_engine(discriminator)
             self.disc_flat = FlatParams(discriminator)
-            self.disc_m = torch.zeros_like(self.disc_flat.data)
-            self.disc_v = torch.zeros_like(self.disc_flat.data)
+            self.disc_m, self.disc_v = self.disc_flat.m, self.disc_flat.v
             self.disc_step = 0             # Adam's count: active steps only (torch skips parameters without a grad)
             dlr = training_cfg.get("disc_lr")
             self.disc_lr = self.lr if dlr is None else float(dlr)
@@ -293,14 +292,15 @@ class VAETrainStep:
             raise
         self.global_step += 1
         from ...runtime import ops
-        n = self.n_trained
-        ops.adamw(self.flat.data[:n], self.flat.grad[:n], self.m[:n], self.v[:n], self.lr, self.betas[0],
-                  self.betas[1], self.eps, self.weight_decay, self.global_step)
+        f, n = self.flat, self.n_trained
+        ops.adamw(f.data[:n], f.grad[:n], self.m[:n], self.v[:n], self.lr, self.betas[0], self.betas[1], self.eps,
+                  self.weight_decay, self.global_step)
         self.eng.invalidate_weights()
         if active:
             self.disc_step += 1
-            ops.adamw(self.disc_flat.data, self.disc_flat.grad, self.disc_m, self.disc_v, self.disc_lr,
-                      self.betas[0], self.betas[1], self.eps, self.disc_weight_decay, self.disc_step)
+            d = self.disc_flat
+            ops.adamw(d.data, d.grad, self.disc_m, self.disc_v, self.disc_lr, self.betas[0], self.betas[1], self.eps,
+                      self.disc_weight_decay, self.disc_step)
             self.disc_eng.invalidate_weights()
         return out
 
@@ -355,8 +355,7 @@ class VAETrainStep:
             from ...runtime.perc_engine import get_perc_engine
             engines.append(get_perc_engine(self.perc))
         for e in engines:
-            e._head_bwd = None
-            e._wq.clear()
+            e.drop_saved_state()
         fold = self.eng._fold
         if fold is not None:
             for p in (fold.weight, fold.bias):
@@ -413,37 +412,14 @@ class VAETrainStep:
         in ``discriminator.parameters()``)."""
         if self.disc is None:
             raise RuntimeError("VAETrainStep.disc_state_dict: no discriminator")
-        params = list(self.disc.parameters())
-        state = {}
-        if self.disc_step > 0:
-            for i, p in enumerate(params):
-                off, n = self.disc_flat.offsets[id(p)]
-                state[i] = {"step": torch.tensor(float(self.disc_step)),
-                            "exp_avg": self.disc_m[off:off + n].view_as(p).detach().cpu().clone(),
-                            "exp_avg_sq": self.disc_v[off:off + n].view_as(p).detach().cpu().clone()}
-        group = {"lr": self.disc_lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.disc_weight_decay,
-                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
-                 "fused": None, "decoupled_weight_decay": True, "params": list(range(len(params)))}
-        return {"state": state, "param_groups": [group]}
+        return self.disc_flat.adamw_state_dict(self.disc_step, lr=self.disc_lr, betas=self.betas, eps=self.eps,
+                                               weight_decay=self.disc_weight_decay)
 
     def load_disc_state_dict(self, sd: Dict[str, Any]) -> None:
         """Inverse of ``disc_state_dict`` (also takes a torch AdamW state of the same discriminator)."""
         if self.disc is None:
             raise RuntimeError("VAETrainStep.load_disc_state_dict: no discriminator")
-        st = sd.get("state", {})
-        steps = 0
-        with torch.no_grad():
-            self.disc_m.zero_()
-            self.disc_v.zero_()
-            for i, p in enumerate(self.disc.parameters()):
-                e = st.get(i) if i in st else st.get(str(i))
-                if not e:
-                    continue
-                off, n = self.disc_flat.offsets[id(p)]
-                self.disc_m[off:off + n].copy_(torch.as_tensor(e["exp_avg"]).reshape(-1))
-                self.disc_v[off:off + n].copy_(torch.as_tensor(e["exp_avg_sq"]).reshape(-1))
-                steps = max(steps, int(float(torch.as_tensor(e["step"]))))
-        self.disc_step = steps
+        self.disc_step = self.disc_flat.load_adamw_state_dict(sd)
         groups = sd.get("param_groups") or []
         if groups:
             self.disc_lr = float(groups[0].get("lr", self.disc_lr))
@@ -452,35 +428,14 @@ class VAETrainStep:
     def state_dict(self) -> Dict[str, Any]:
         """The optimizer state in ``torch.optim.AdamW.state_dict()`` form (state keyed by the index in
         ``model.parameters()``) plus ``global_step``."""
-        params = list(self.model.parameters())
-        state = {}
-        if self.global_step > 0:
-            for i, p in enumerate(params):
-                off, n = self.flat.offsets[id(p)]
-                state[i] = {"step": torch.tensor(float(self.global_step)),
-                            "exp_avg": self.m[off:off + n].view_as(p).detach().cpu().clone(),
-                            "exp_avg_sq": self.v[off:off + n].view_as(p).detach().cpu().clone()}
-        group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay,
-                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
-                 "fused": None, "decoupled_weight_decay": True, "params": list(range(len(params)))}
-        return {"state": state, "param_groups": [group], "global_step": self.global_step}
+        sd = self.flat.adamw_state_dict(self.global_step, lr=self.lr, betas=self.betas, eps=self.eps,
+                                        weight_decay=self.weight_decay)
+        sd["global_step"] = self.global_step
+        return sd
 
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
         """Inverse of ``state_dict`` (also takes a torch AdamW state of the same model)."""
-        params = list(self.model.parameters())
-        st = sd.get("state", {})
-        steps = 0
-        with torch.no_grad():
-            self.m.zero_()
-            self.v.zero_()
-            for i, p in enumerate(params):
-                e = st.get(i) if i in st else st.get(str(i))
-                if not e:
-                    continue
-                off, n = self.flat.offsets[id(p)]
-                self.m[off:off + n].copy_(torch.as_tensor(e["exp_avg"]).reshape(-1))
-                self.v[off:off + n].copy_(torch.as_tensor(e["exp_avg_sq"]).reshape(-1))
-                steps = max(steps, int(float(torch.as_tensor(e["step"]))))
+        steps = self.flat.load_adamw_state_dict(sd)
         self.global_step = int(sd.get("global_step", steps))
         groups = sd.get("param_groups") or []
         if groups:

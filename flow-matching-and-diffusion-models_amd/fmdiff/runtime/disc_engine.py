@@ -211,7 +211,7 @@ class DiscEngine(LayerEngine):
             self._join()
             self._land(landed)
         except BaseException:
-            self._wq.clear()   # a failed backward leaves no weight gradient queued for the next one
+            self.drop_saved_state()   # a failed backward leaves nothing behind for the next one
             raise
         return dx
 

@@ -396,6 +396,12 @@ class LayerEngine:
     def invalidate_weights(self):
         self.wc.invalidate()
 
+    def drop_saved_state(self):
+        """Nothing of a forward or a failed backward is left for the next one: the head's backward slot and the
+        queued weight gradients."""
+        self._head_bwd = None
+        self._wq.clear()
+
     # ------------------------------------------------------------- layers
     def _replay(self, ctx: Ctx, o: Act, layer) -> Act:
         """``o``: the output of a layer that ran on a forward-only kernel, which keeps nothing for a backward.
@@ -1332,7 +1338,7 @@ class UNetEngine(LayerEngine):
                 # captured form is bit-equal to the single graph)
                 self._join()
         except BaseException:
-            self._wq.clear()   # a failed backward leaves no weight gradient queued for the next one
+            self.drop_saved_state()   # a failed backward leaves nothing behind for the next one
             raise
         finally:
             ops.gb_flush()

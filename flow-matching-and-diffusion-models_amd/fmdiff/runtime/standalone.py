@@ -104,7 +104,7 @@ class _BlockFunction(torch.autograd.Function):
             for fn in reversed(ctx.tape):
                 fn()
         except BaseException:
-            eng._wq.clear()   # a failed backward leaves no weight gradient queued for the next one
+            eng.drop_saved_state()   # a failed backward leaves nothing behind for the next one
             raise
         finally:
             ops.gb_flush()

@@ -225,7 +225,7 @@ class VAEEngine(LayerEngine):
                 fn()
             self._join()
         except BaseException:
-            self._wq.clear()   # a failed backward leaves no weight gradient queued for the next one
+            self.drop_saved_state()   # a failed backward leaves nothing behind for the next one
             raise
         finally:
             ops.gb_flush()

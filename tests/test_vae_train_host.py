@@ -1,5 +1,6 @@
 """CPU checks of the AutoencoderKL training path's host side: the unfold algebra, the C ABI of the latent 1x1
-backward, the absence of a CPU path and the configurations that are refused."""
+backward, the absence of a CPU path, the configurations that are refused, and the flat AdamW state (``FlatParams``)
+against ``torch.optim.AdamW``'s own ``state_dict()``."""
 import ctypes
 import os
 import re
@@ -138,3 +139,99 @@ def test_train_step_state_dict_round_trip():
     other.load_state_dict(sd)
     assert other.global_step == 7 and other.lr == 3e-4 and other.weight_decay == 0.01
     assert torch.equal(other.m, st.m) and torch.equal(other.v, st.v)
+
+
+# ------------------------------------------------------- FlatParams: the one owner of the torch AdamW state format
+HYPER = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)
+
+
+def _two_layer(seed=3):
+    torch.manual_seed(seed)
+    return torch.nn.Sequential(torch.nn.Linear(3, 4), torch.nn.Linear(4, 2))
+
+
+@pytest.fixture(scope="module")
+def torch_adamw():
+    """A twin under torch.optim.AdamW after two steps on seeded random gradients: (twin, optimizer, state_dict)."""
+    twin = _two_layer()
+    opt = torch.optim.AdamW(twin.parameters(), lr=1e-3, weight_decay=0.01)
+    g = torch.Generator().manual_seed(4)
+    for _ in range(2):
+        for p in twin.parameters():
+            p.grad = torch.randn(p.shape, generator=g)
+        opt.step()
+    return twin, opt, opt.state_dict()
+
+
+def _slices(flat, model):
+    out = []
+    for p in model.parameters():
+        off, n = flat.offsets[id(p)]
+        out.append((flat.m[off:off + n].view_as(p), flat.v[off:off + n].view_as(p)))
+    return out
+
+
+def test_flat_adamw_state_against_torch(torch_adamw):
+    from fmdiff.pipelines.train.fused import FlatParams
+    twin, opt, sd = torch_adamw
+    model = _two_layer()
+    flat = FlatParams(model)
+    assert flat.load_adamw_state_dict(sd) == 2
+    for i, (m, v) in enumerate(_slices(flat, model)):
+        assert torch.equal(m, sd["state"][i]["exp_avg"]) and torch.equal(v, sd["state"][i]["exp_avg_sq"])
+    out = flat.adamw_state_dict(2, **HYPER)
+    assert sorted(out) == ["param_groups", "state"] and sorted(out["state"]) == sorted(sd["state"])
+    for i, want in sd["state"].items():
+        assert sorted(out["state"][i]) == sorted(want)
+        for k, t in want.items():
+            got = out["state"][i][k]
+            assert got.dtype == t.dtype and got.shape == t.shape and got.device == t.device and torch.equal(got, t), k
+            assert got.data_ptr() not in (flat.m.data_ptr(), flat.v.data_ptr())
+    (group,), (want,) = out["param_groups"], sd["param_groups"]
+    assert set(group) == set(want)
+    assert group == want   # the values too: torch's defaults, the hyperparameters passed, the parameter indices
+    with_lr = flat.adamw_state_dict(2, **HYPER, initial_lr=2e-3)["param_groups"][0]
+    assert set(with_lr) == set(want) | {"initial_lr"} and with_lr["initial_lr"] == 2e-3
+    torch.optim.AdamW(twin.parameters(), lr=1.0).load_state_dict(out)
+    fresh = torch.optim.AdamW(_two_layer().parameters(), lr=1.0)
+    fresh.load_state_dict(out)
+    for p, (m, v) in zip(fresh.param_groups[0]["params"], _slices(flat, model)):
+        assert torch.equal(fresh.state[p]["exp_avg"], m) and torch.equal(fresh.state[p]["exp_avg_sq"], v)
+        assert float(fresh.state[p]["step"]) == 2.0
+    assert fresh.param_groups[0]["lr"] == 1e-3 and fresh.param_groups[0]["weight_decay"] == 0.01
+
+
+def test_flat_adamw_load_zeroes_first(torch_adamw):
+    from fmdiff.pipelines.train.fused import FlatParams
+    sd = torch_adamw[2]
+    partial = {"state": {i: e for i, e in sd["state"].items() if i != 1}, "param_groups": sd["param_groups"]}
+    model = _two_layer()
+    flat = FlatParams(model)
+    flat.m.fill_(1.0)
+    flat.v.fill_(1.0)
+    assert flat.load_adamw_state_dict(partial) == 2
+    for i, (m, v) in enumerate(_slices(flat, model)):
+        if i == 1:
+            assert not m.any() and not v.any()
+        else:
+            assert torch.equal(m, sd["state"][i]["exp_avg"]) and torch.equal(v, sd["state"][i]["exp_avg_sq"])
+
+
+def test_flat_adamw_load_takes_string_keys(torch_adamw):
+    from fmdiff.pipelines.train.fused import FlatParams
+    sd = torch_adamw[2]
+    a, b = FlatParams(_two_layer()), FlatParams(_two_layer())
+    assert a.load_adamw_state_dict(sd) == 2
+    assert b.load_adamw_state_dict({"state": {str(i): e for i, e in sd["state"].items()},
+                                    "param_groups": sd["param_groups"]}) == 2
+    assert a.m.any() and torch.equal(a.m, b.m) and torch.equal(a.v, b.v)
+
+
+def test_flat_adamw_state_is_empty_at_step_zero():
+    from fmdiff.pipelines.train.fused import FlatParams
+    flat = FlatParams(_two_layer())
+    flat.m.fill_(1.0)   # whatever the buffers hold: no step, no state, as a fresh torch optimizer
+    out = flat.adamw_state_dict(0, **HYPER)
+    assert out["state"] == {} and out["param_groups"][0]["params"] == [0, 1, 2, 3]
+    assert flat.load_adamw_state_dict(out) == 0 and not flat.m.any()
+    assert flat.load_adamw_state_dict(None) == 0
